@@ -6,7 +6,9 @@ Workload (BASELINE.json configs[1], the configuration the metric is quoted on fo
        group by k insert into O` over (k int, v double, ts long), 100k uniform keys,
        1,000,000 events per event-time second, one InputHandler.send per event (PER_EVENT clock).
 A step = one sh_push_device of `--batch` events (inputs already resident in HBM; the window state,
-key table and outputs stay on the device).
+key table and outputs stay on the device). On one GPU at most `--resident` batches of the stream are in HBM
+at a time: a longer run is timed in segments of that many pushes (each from its first push to the device
+synchronisation after its last), and the next slice of the same stream is generated between them, untimed.
 
 N > 1 (`--ingest slice`, the default; north_star / SURVEY.md §8e): ONE global stream with N x the
 keys and N x the event rate; every step each rank ingests a contiguous slice of `--batch` events,
@@ -15,7 +17,11 @@ re-keyed to the GPU owning its key over an RCCL all-to-all (xGMI), then aggregat
 (sh_shard_*). Per-GPU work equals the N = 1 configuration (weak scaling). `--ingest keyed` instead
 gives each rank its own pre-partitioned stream (no data-path collective).
 
-Launch: python bench.py [--gpus 1 --steps K --warmup W]
+A plain run sets up, warms up, times `--steps` steps and prints the line. `--full` adds what takes
+runs of its own: the first warm-up push's digest against the oracle's golden digest, the host-fed
+(PCIe) leg and the CPU baselines. `--dump-outputs DIR` writes the last timed step's output arrays.
+
+Launch: python bench.py [--gpus 1 --steps K --warmup W] [--full] [--dump-outputs DIR]
    or:  python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 Rank 0 prints ONE JSON line.
 """
@@ -38,7 +44,18 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the output digest check against the "
+                         "oracle's golden digest, the host-fed (PCIe) leg and the CPU baselines (one core, all cores)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's output (the sh_out arrays a caller of "
+                         "the push receives) as DIR/<name>.npy in float64; more than 48 MB in all is cut "
+                         "to a fixed seeded sample of the rows (one GPU, device-resident query workloads)")
     ap.add_argument("--batch", type=int, default=1 << 25, help="events per step (per GPU)")
+    ap.add_argument("--resident", type=int, default=128, metavar="R",
+                    help="C2 on one GPU: input batches resident in HBM at a time (28 B per event: 0.94 GB per batch "
+                         "of 2^25). More steps + warm-ups than R run in segments of R pushes, every push timed, the "
+                         "next segment's slice of the same stream generated between the timed segments")
     ap.add_argument("--keys", type=int, default=100_000)
     ap.add_argument("--keys-total", type=int, default=0,
                     help="N > 1 slice ingest (and --shard-loopback): the global key count (default N x --keys; "
@@ -49,8 +66,8 @@ def parse():
     ap.add_argument("--events-per-ms", type=int, default=1000)
     ap.add_argument("--send-size", type=int, default=1, help="events per InputHandler.send (1 = PER_EVENT)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the oracle CPU baseline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the host-fed (PCIe) leg of the default line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-pcie", action="store_true", help="--full without the host-fed (PCIe) leg")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="N > 1 slice ingest: exchange and consume each push in turn (no overlap)")
     ap.add_argument("--ingest", choices=["slice", "keyed"], default="slice",
@@ -67,7 +84,13 @@ def parse():
                          "(PCIe-inclusive rate, H2D GB/s, per-call latency); never the headline value")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="torch.distributed backend (nccl = RCCL over xGMI; gloo only to rehearse N>1 on one GPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus != 1 or args.host or args.shard_loopback or args.workload == "c4"):
+        ap.error("--dump-outputs writes the output of a device-resident query on one GPU "
+                 "(not --gpus N > 1, --host, --shard-loopback or --workload c4)")
+    return args
 
 
 def cpu_baseline(args):
@@ -175,6 +198,43 @@ def output_digest_check(args, arrays, golden=GOLDEN_DIGEST, c1_batch=None):
     got = digest.output_digest(arrays)
     return {"match": got == gold["push0"]["sha256"], "sha256": got, "rows": int(arrays["ts"].size),
             "expected": gold["push0"]["sha256"], "source": golden + " (oracle/ on the same stream)"}
+
+
+DUMP_MAX_BYTES = 48 << 20  # of the 64 MB a dump may take
+DUMP_SEED = 0xD0
+
+
+def dump_outputs(dirname, a):
+    """Write a runtime.device_out_arrays dict as DIR/<name>.npy, every array in float64 (timestamps, keys,
+    counts and stream indices are far below 2^53; an aggregate is decoded from its 8-byte pattern by its
+    type). The row arrays share one row selection and the two flush arrays one flush selection: everything
+    when that fits DUMP_MAX_BYTES, else a sorted sample drawn with a fixed seed (so two builds given the same
+    arguments write the same rows), whose indices are written as rows_index / flushes_index."""
+    import numpy as np
+    from siddhi_amd import abi
+    os.makedirs(dirname, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def select(n, n_arrays, budget):
+        cap = max(1, budget // (8 * (n_arrays + 1)))
+        return np.arange(n, dtype=np.int64) if n <= cap else np.sort(rng.choice(n, size=cap, replace=False))
+
+    n, nk, na = a["ts"].size, a["keys"].shape[0], a["vals"].shape[0]
+    rows = select(n, 3 + nk + 2 * na, DUMP_MAX_BYTES * 3 // 4)
+    out = {"rows_index": rows, "ts": a["ts"][rows], "expired": a["expired"][rows], "rep": a["rep"][rows]}
+    for k in range(nk):
+        out[f"key{k}"] = a["keys"][k][rows]
+    for v in range(na):
+        bits = np.ascontiguousarray(a["vals"][v][rows])
+        out[f"val{v}"] = bits.view(np.float64 if a["val_types"][v] in (abi.DOUBLE, abi.FLOAT) else np.int64)
+        out[f"null{v}"] = a["nulls"][v][rows]
+    nf = a["flush_clock"].size
+    fl = select(nf, 2, DUMP_MAX_BYTES // 4)
+    offs = np.asarray(a["flush_offsets"], dtype=np.int64)
+    out.update(flushes_index=fl, flush_rows=np.diff(offs)[fl], flush_clock=np.asarray(a["flush_clock"])[fl],
+               n_rows=np.array([n]), n_flushes=np.array([nf]))
+    for name, arr in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(arr).astype(np.float64))
 
 
 # ---- secondary single-GPU workloads (BASELINE.json configs[0], [2], [3]; externalTimeBatch) ---------
@@ -311,7 +371,7 @@ def run_secondary(args, dev, rank=0, world=1, dist=None):
     digest_check = None
     for i in range(args.warmup):
         op = push(i)
-        if i == 0 and args.workload == "c1" and not sliced:
+        if i == 0 and args.full and args.workload == "c1" and not sliced:
             torch.cuda.synchronize()
             digest_check = output_digest_check(args, runtime.device_out_arrays(op), C1_GOLDEN_DIGEST, B)
     torch.cuda.synchronize()
@@ -325,8 +385,9 @@ def run_secondary(args, dev, rank=0, world=1, dist=None):
         dist.barrier()
     torch.cuda.synchronize()
     kern_ms, t0 = 0.0, time.perf_counter()
+    op = None
     for i in range(args.warmup, nb):
-        push(i)
+        op = push(i)
         if not sliced and not agg_timed:
             st = q.stats()
             # the whole device pipeline of the push (HIP events around it on the library's stream): the
@@ -348,6 +409,8 @@ def run_secondary(args, dev, rank=0, world=1, dist=None):
     if rank != 0:
         q.close()
         return
+    if args.dump_outputs and op is not None:
+        dump_outputs(args.dump_outputs, runtime.device_out_arrays(op, args.workload in ("c3all", "plb", "plg")))
     desc, bpe = SECONDARY[args.workload]
     roof = None
     if kern_ms > 0:
@@ -573,8 +636,8 @@ def main():
     args = parse()
     # all-cores CPU baseline workers: started before anything touches the GPU (rank 0, N = 1 only)
     pool, P = None, 0
-    if (not args.no_cpu_baseline and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.workload == "c2"
-            and not args.host):
+    if (args.full and not args.no_cpu_baseline and int(os.environ.get("WORLD_SIZE", "1")) == 1
+            and args.workload == "c2" and not args.host):
         import multiprocessing as mp
         P = max(2, min(15, os.cpu_count() or 2))
         # the workers run the oracle only: they must not load a HIP runtime (siddhi_amd binds one at
@@ -621,7 +684,11 @@ def main():
                          aggs=[("count", None), ("min", "v"), ("max", "v"), ("avg", "v")], key_capacity=cap)
     B = args.batch
     nb = args.warmup + args.steps
-    batches = []
+    # batches [lo, hi) of the stream are resident at a time (load()): all of them, as one segment, when they fit
+    # --resident; else the steps run segment by segment, each timed from its first push to the device
+    # synchronisation after its last, the next segment's inputs generated in between (untimed)
+    R = nb if world > 1 else max(1, args.resident)
+    batches, descs = {}, {}
     if sliced:
         # rank r's slice of global push i: events [(i*N + r)*B, (i*N + r + 1)*B) of one stream
         from siddhi_amd.shard import PipelinedPush, ShardedQuery, TorchExchange, distributed_push
@@ -630,21 +697,26 @@ def main():
         send_buf = torch.empty(B * q.record_bytes, dtype=torch.uint8, device=dev)
         # the record exchange of push i overlaps the consume of push i - 1 (two send buffers)
         pp = None if args.no_pipeline else PipelinedPush(q, ex, [send_buf, torch.empty_like(send_buf)])
-        for i in range(nb):
-            batches.append(synth.torch_keyed_stream((i * world + rank) * B, B, 0xC2, keys_total,
-                                                    args.events_per_ms * world, dev))
     else:
         # keyed: this rank's own stream; keys offset so ranks own disjoint keys
         q = runtime.GpuQuery(spec, ctx)
-        for i in range(nb):
+
+    def load(lo, hi):
+        """Make batches [lo, hi) resident in place of the previous ones (whose memory is reused)."""
+        batches.clear()
+        descs.clear()
+        for i in range(lo, hi):
+            if sliced:
+                batches[i] = synth.torch_keyed_stream((i * world + rank) * B, B, 0xC2, keys_total,
+                                                      args.events_per_ms * world, dev)
+                continue
             ts, cols = synth.torch_keyed_stream(i * B, B, 0xC2 ^ (rank * 0x9E37), args.keys, args.events_per_ms, dev)
             if rank:
                 cols[0] += rank * args.keys
-            batches.append((ts, cols))
-        # the batch descriptors, built once (a host shim keeps one per buffer)
-        descs = [q.device_batch(B, ts.data_ptr(), [c.data_ptr() for c in cols], args.send_size)
-                 for ts, cols in batches]
-    torch.cuda.synchronize()
+            batches[i] = (ts, cols)
+            # the batch descriptor, built once (a host shim keeps one per buffer)
+            descs[i] = q.device_batch(B, ts.data_ptr(), [c.data_ptr() for c in cols], args.send_size)
+        torch.cuda.synchronize()
 
     def push(i):
         """The output of push i (pipelined sharded ingest: of push i - 1, None for the first)."""
@@ -666,51 +738,65 @@ def main():
 
     phases, timing = {}, False
     digest_check = None
-    for i in range(args.warmup):
-        op = push(i)
-        if i == 0 and not sliced and world == 1 and op is not None:
-            torch.cuda.synchronize()
-            digest_check = output_digest_check(args, runtime.device_out_arrays(op))
-    drain()
-    torch.cuda.synchronize()
-    timing = True
-    if dist:
-        dist.barrier()
-    torch.cuda.synchronize()
     kern_ms, kern_bytes, flushes, rows = 0.0, 0, 0, 0
     host_t = [] if os.environ.get("SH_TIMING") else None
-    t0 = time.perf_counter()
-    for i in range(args.warmup, nb + 1):
-        ta = time.perf_counter()
-        op = push(i) if i < nb else drain()  # (the pipelined ingest consumes its last push here)
-        tb = time.perf_counter()
-        if op is None:
+    last_op = None
+    elapsed, loop_s, sync_s = 0.0, 0.0, 0.0
+    for lo in range(0, nb, R):
+        hi = min(nb, lo + R)
+        load(lo, hi)
+        for i in range(lo, min(hi, args.warmup)):
+            op = push(i)
+            if i == 0 and args.full and not sliced and world == 1 and op is not None:
+                torch.cuda.synchronize()
+                digest_check = output_digest_check(args, runtime.device_out_arrays(op))
+        if hi <= args.warmup:
             continue
-        o = op.contents
-        st = q.stats()
-        kern_ms += st.main_kernel_ms
-        flushes += o.n_flushes
-        rows += o.n_rows
-        if host_t is not None:
-            host_t.append((tb - ta, time.perf_counter() - tb))
-    t_sync = time.perf_counter()
-    torch.cuda.synchronize()
+        if not timing:  # the warm-up is over
+            drain()
+            torch.cuda.synchronize()
+            timing = True
+            if dist:
+                dist.barrier()
+            torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(max(lo, args.warmup), hi + (hi == nb)):
+            ta = time.perf_counter()
+            op = push(i) if i < nb else drain()  # (the pipelined ingest consumes its last push here)
+            tb = time.perf_counter()
+            if op is None:
+                continue
+            last_op = op
+            o = op.contents
+            st = q.stats()
+            kern_ms += st.main_kernel_ms
+            flushes += o.n_flushes
+            rows += o.n_rows
+            if host_t is not None:
+                host_t.append((tb - ta, time.perf_counter() - tb))
+        t_sync = time.perf_counter()
+        torch.cuda.synchronize()
+        loop_s += t_sync - t0
+        sync_s += time.perf_counter() - t_sync
+        if dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+        elapsed += time.perf_counter() - t0
     if host_t:
         import statistics
-        print(f"[bench timing] loop {(t_sync - t0) * 1e3:.2f} ms, pushes {sum(a for a, _ in host_t) * 1e3:.2f} ms, "
-              f"bookkeeping {sum(b for _, b in host_t) * 1e3:.2f} ms, final sync {(time.perf_counter() - t_sync) * 1e3:.2f} ms",
+        print(f"[bench timing] loop {loop_s * 1e3:.2f} ms, pushes {sum(a for a, _ in host_t) * 1e3:.2f} ms, "
+              f"bookkeeping {sum(b for _, b in host_t) * 1e3:.2f} ms, final sync {sync_s * 1e3:.2f} ms",
               file=sys.stderr)
         print(f"[bench timing] push call median {statistics.median(a for a, _ in host_t) * 1e6:.1f} us, "
               f"bookkeeping median {statistics.median(b for _, b in host_t) * 1e6:.1f} us; per push: "
               + " ".join(f"{a * 1e6:.0f}" for a, _ in host_t), file=sys.stderr)
     if dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
-    if dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and last_op is not None:
+        # the last timed push's sh_out is still the query's current output (nothing was pushed since)
+        dump_outputs(args.dump_outputs, runtime.device_out_arrays(last_op))
     total_events = B * args.steps * world
     # roofline of the dominant kernel (k_aggregate): algorithmic bytes per launch / its HIP-event time
     n_launch = args.steps
@@ -757,9 +843,9 @@ def main():
         # rank 0's wall time per step in each phase of the sharded push (summaries all-gather,
         # pack, record all-to-all over RCCL, owner pipeline) and its bytes sent per step
         result["config"]["phases_ms_per_step_rank0"] = {k: v / args.steps for k, v in phases.items()}
-    if rank == 0 and world == 1 and not sliced and not args.no_pcie:
+    if args.full and rank == 0 and world == 1 and not sliced and not args.no_pcie:
         result["pcie"] = pcie_line(args, dev, ctx)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args)
         if pool is not None:
             result["cpu_baseline_all_cores"] = cpu_baseline_all_cores(args, pool, P)

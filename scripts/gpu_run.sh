@@ -4,7 +4,8 @@
 # STEPs (run in order, each under its own time limit; the first failure ends the call):
 #   tests[=EXPR]        pytest -m gpu (optionally -k EXPR) -> gpurun_out/TAG_tests.log
 #   smoke               __graft_entry__.smoke()
-#   bench[=WL]          bench.py line (default workload, with cpu_baseline) or --workload WL
+#   bench[=WL]          bench.py --full line (default workload, with cpu_baseline) or --workload WL
+#                       (every bench.py call below passes --full: digest check and host-fed leg as before)
 #   kstats=WL           rocprofv3 --kernel-trace --stats of bench.py --workload WL -> TAG_WL_kernel_stats.txt
 #   pmc=WL              FETCH_SIZE and WRITE_SIZE passes (separate runs) -> TAG_WL_pmc.json
 #   shard=WL            bench.py --workload WL --shard-loopback G=8 (one-GPU sharded pipeline phases)
@@ -34,14 +35,14 @@ for step in "$@"; do
     bench)
       n=${arg:-c2}
       extra="--no-cpu-baseline"; [ -z "$arg" ] && extra=""
-      timeout -k 10 400 python -u bench.py $(wl_args "$arg") $extra ${BENCH_ARGS:-} > "${O}_${n}_bench.json" 2> "${O}_${n}_bench.err" \
+      timeout -k 10 400 python -u bench.py --full $(wl_args "$arg") $extra ${BENCH_ARGS:-} > "${O}_${n}_bench.json" 2> "${O}_${n}_bench.err" \
           || fail "bench $n" "${O}_${n}_bench.err"
       python3 -c "import json,sys; d=json.load(open(sys.argv[1])); r=d.get('roofline') or {}; print(sys.argv[2], '%.3e' % d['value'], d['ms_per_step'], 'sha', d.get('output_sha256_match'), 'frac', r.get('frac'))" \
           "${O}_${n}_bench.json" "$n" ;;
     kstats)
       n=${arg:-c2}
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$P/kt_$n" -o run --output-format csv -- \
-          python3 bench.py $(wl_args "$arg") --steps 5 --warmup 2 --no-cpu-baseline ${BENCH_ARGS:-} > "$P/kt_$n.json" 2> "$P/kt_$n.err" \
+          python3 bench.py --full $(wl_args "$arg") --steps 5 --warmup 2 --no-cpu-baseline ${BENCH_ARGS:-} > "$P/kt_$n.json" 2> "$P/kt_$n.err" \
           || fail "kstats $n" "$P/kt_$n.err"
       python3 scripts/kstats.py "$P/kt_$n" > "${O}_${n}_kernel_stats.txt" || fail "kstats summary $n"
       head -8 "${O}_${n}_kernel_stats.txt" ;;
@@ -49,7 +50,7 @@ for step in "$@"; do
       n=${arg:-c2}
       for ctr in FETCH_SIZE WRITE_SIZE; do
         timeout -s KILL 150 rocprofv3 --pmc $ctr -d "$P/${n}_$ctr" -o run --output-format csv -- \
-            python3 bench.py $(wl_args "$arg") --steps 2 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > /dev/null 2> "$P/${n}_$ctr.err" \
+            python3 bench.py --full $(wl_args "$arg") --steps 2 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > /dev/null 2> "$P/${n}_$ctr.err" \
             || fail "pmc $n $ctr" "$P/${n}_$ctr.err"
       done
       F=$(python3 -c "import glob,sys;print(glob.glob(sys.argv[1]+'/**/run_counter_collection.csv',recursive=True)[0])" "$P/${n}_FETCH_SIZE")
@@ -60,18 +61,18 @@ for step in "$@"; do
       n=${arg:-c2}
       first=${TL_FIRST:-k_boundaries}
       timeout -k 10 300 rocprofv3 --kernel-trace -d "$P/tl_$n" -o run --output-format csv -- \
-          python3 bench.py $(wl_args "$arg") --steps 5 --warmup 2 --no-cpu-baseline ${BENCH_ARGS:-} > "$P/tl_$n.json" 2> "$P/tl_$n.err" \
+          python3 bench.py --full $(wl_args "$arg") --steps 5 --warmup 2 --no-cpu-baseline ${BENCH_ARGS:-} > "$P/tl_$n.json" 2> "$P/tl_$n.err" \
           || fail "timeline $n" "$P/tl_$n.err"
       python3 scripts/timeline.py "$P/tl_$n" "$first" > "${O}_${n}_timeline.txt" || fail "timeline summary $n"
       tail -1 "${O}_${n}_timeline.txt" ;;
     htiming)
       n=${arg:-c2}
-      SH_TIMING=1 timeout -k 10 300 python -u bench.py $(wl_args "$arg") --steps 20 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} \
+      SH_TIMING=1 timeout -k 10 300 python -u bench.py --full $(wl_args "$arg") --steps 20 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} \
           > "${O}_${n}_htiming.json" 2> "${O}_${n}_htiming.txt" || fail "htiming $n" "${O}_${n}_htiming.txt"
       grep "sh timing" "${O}_${n}_htiming.txt" | head -12 ;;
     shard)
       n=${arg:-c2}
-      timeout -k 10 400 python -u bench.py $(wl_args "$arg") --shard-loopback 8 --steps 5 --warmup 2 --no-cpu-baseline \
+      timeout -k 10 400 python -u bench.py --full $(wl_args "$arg") --shard-loopback 8 --steps 5 --warmup 2 --no-cpu-baseline \
           > "${O}_${n}_shard.json" 2> "${O}_${n}_shard.err" || fail "shard $n" "${O}_${n}_shard.err"
       cat "${O}_${n}_shard.json" ;;
     *) echo "unknown step $step"; exit 2 ;;
