@@ -62,11 +62,14 @@ extern "C" {
 #define SH_OP_AND 9
 #define SH_OP_OR 10
 #define SH_OP_NOT 11
+/* operands of a having program only (sh_query_set_having) */
+#define SH_OP_KEY 12  /* push group-by column number `col` (its stream type)                */
+#define SH_OP_AGG 13  /* push aggregate number `col` (the type sh_out.val_types reports)    */
 
 typedef struct {
     int32_t op;
     int32_t type; /* SH_T_* of the constant (SH_OP_CONST)                                  */
-    int32_t col;  /* column index (SH_OP_COL)                                              */
+    int32_t col;  /* column index (SH_OP_COL); group-by / aggregate number (SH_OP_KEY / SH_OP_AGG) */
     int32_t pad;
     int64_t ival;
     double dval;
@@ -267,6 +270,36 @@ int sh_query_set_output_rate(sh_query* q, int32_t kind, int64_t n);
  * The limiter's kernels run on q's device. */
 int sh_rate_apply_merged(sh_query* q, const sh_out* merged, const sh_out** out);
 
+/* The `having` condition of a batch-window query, on the GPU. QuerySelector.processInBatchGroupBy
+ * (core/query/selector/QuerySelector.java:315-374) runs the condition after every event of a chunk, on the
+ * key's running aggregates, and keeps the event only when it holds (processInBatchNoGroupBy :271-313 the same
+ * with one implicit key): a key's row carries the values and the representative event of its LAST PASSING
+ * event, stands at the position of its FIRST PASSING event, a key that never passes emits nothing, and a
+ * chunk that keeps no row gives no flush. The library reproduces exactly that — it never tests the condition
+ * once on a key's final row.
+ * The program is a postfix sh_filter_op array like the filter: SH_OP_KEY, SH_OP_AGG, SH_OP_CONST, the six
+ * comparisons (Compare executors' promotion as for the filter; a null operand would make a comparison false,
+ * CompareConditionExpressionExecutor.java:38-42 — batch-window aggregates are never null) and AND / OR / NOT;
+ * at most 32 ops, boolean result. It is copied. Set once, before the first push (SH_ERR_STATE later or twice);
+ * n_ops == 0 is SH_ERR_INVALID.
+ * SH_ERR_INVALID: stack underflow or values left on the stack, a key / aggregate number out of range, a result
+ * that is not boolean, a boolean fed to a comparison, a relational comparison on a string-id or bool operand,
+ * more than 32 ops. SH_ERR_UNSUPPORTED, the message naming the shape (the query then stays on the CPU): window
+ * NONE / TIME / EXT_TIME (sliding windows), expired or all-events output, a partitioned query, a group-by
+ * the library interns (wide keys), no aggregator, an SH_OP_COL operand (a stream attribute of the
+ * representative event). Supported: lengthBatch, timeBatch and externalTimeBatch, plain or with
+ * stream.current.event, grouped or not, current-events output. On a live query a having program and
+ * sh_query_set_ext_timeout, or sh_query_set_ext_replace_ts, refuse each other in either order
+ * (SH_ERR_UNSUPPORTED). A having query always gets the full host flush arrays (as a rate-limited query does):
+ * sh_query_set_compact_flushes / sh_query_set_device_flushes are ignored for it; the row arrays of
+ * sh_push_device stay on the device. An output rate limiter sees the having-filtered rows.
+ * Both entry points were added without a change of SH_ABI_VERSION or of any struct: a caller detects them by
+ * symbol lookup (dlsym / SymbolLookup). */
+int sh_query_set_having(sh_query* q, const sh_filter_op* ops, int32_t n_ops);
+/* The verdict sh_query_set_having would give on a query created from `desc`, without a context or a GPU
+ * (the same validation code): the shim calls it at parse time to decide whether the query goes to the GPU. */
+int sh_having_check(const sh_query_desc* desc, const sh_filter_op* ops, int32_t n_ops);
+
 /* externalTimeBatch's fourth parameter, the scheduler timeout in milliseconds
  * (ExternalTimeBatchWindowProcessor.java:196-207, `externalTimeBatch(ts, 1 sec, 0, 6 sec)`): when the
  * playback clock passes the last scheduled time (clock of the window's first event, of every batch
@@ -322,7 +355,9 @@ int sh_query_set_strings(sh_query* q, int32_t col, int64_t first_id, int64_t n, 
  * key's aggregator state and min/max deques, the partition key, the playback clock and
  * nextEmitTime. Two calls: buf = NULL returns the size in *len. A blob restores only into a query
  * created from the same descriptor (SH_ERR_INVALID otherwise); the restored query then continues
- * exactly as the snapshotted one would have. */
+ * exactly as the snapshotted one would have. A having program (sh_query_set_having) is configuration, not
+ * state: it is neither stored nor fingerprinted; the caller sets it again on the new query before
+ * sh_query_restore. */
 int sh_query_snapshot(sh_query* q, void* buf, int64_t cap, int64_t* len);
 int sh_query_restore(sh_query* q, const void* buf, int64_t len);
 
@@ -411,6 +446,8 @@ typedef struct {
 } sh_bound;
 
 typedef struct sh_shard sh_shard;
+/* A sharded query has no way to carry a having program (sh_query_set_having takes an sh_query): a query
+ * with `having` is not sharded. */
 int sh_shard_create(sh_ctx* ctx, const sh_query_desc* desc, int32_t rank, int32_t world, sh_shard** out);
 int sh_shard_destroy(sh_shard* s);
 /* Bytes per packed event record at most (depends on the query's value columns; a push whose events

@@ -25,6 +25,7 @@ TYPE_NAMES = {"int": INT, "long": LONG, "float": FLOAT, "double": DOUBLE, "strin
 NP_DTYPE = {INT: np.int32, LONG: np.int64, FLOAT: np.float32, DOUBLE: np.float64, STRID: np.int32, BOOL: np.uint8}
 
 OP_COL, OP_CONST, OP_GT, OP_GE, OP_LT, OP_LE, OP_EQ, OP_NE, OP_AND, OP_OR, OP_NOT = range(1, 12)
+OP_KEY, OP_AGG = 12, 13  # operands of a having program (sh_query_set_having)
 CMP_OPS = {">": OP_GT, ">=": OP_GE, "<": OP_LT, "<=": OP_LE, "==": OP_EQ, "!=": OP_NE}
 
 WIN_NONE, WIN_LENGTH_BATCH, WIN_TIME_BATCH, WIN_TIME, WIN_EXT_TIME_BATCH, WIN_EXT_TIME = 0, 1, 2, 3, 4, 5
@@ -157,6 +158,53 @@ def compile_filter(schema: Schema, expr) -> List[FilterOp]:
     return ops
 
 
+def compile_having(spec, expr) -> List[FilterOp]:
+    """Compile a `having` condition into the postfix program of sh_query_set_having.
+
+    The tuple syntax of compile_filter; operands are ("agg", i) — aggregate number i of spec.aggs —,
+    ("key", i) — group-by column number i —, typed constants ("long", 2) / ("double", 1.5) or bare Python
+    numbers (int -> INT, or LONG beyond 32 bits; float -> DOUBLE). `spec` is the query the program belongs
+    to (the library checks the numbers and types against its descriptor)."""
+    ops: List[FilterOp] = []
+
+    def operand(x):
+        if isinstance(x, tuple) and len(x) == 2 and x[0] == "agg":
+            ops.append(FilterOp(op=OP_AGG, col=int(x[1])))
+        elif isinstance(x, tuple) and len(x) == 2 and x[0] == "key":
+            ops.append(FilterOp(op=OP_KEY, col=int(x[1])))
+        elif isinstance(x, tuple) and len(x) == 2 and x[0] in TYPE_NAMES:
+            t = TYPE_NAMES[x[0]]
+            if t in (FLOAT, DOUBLE):
+                ops.append(FilterOp(op=OP_CONST, type=t, dval=float(x[1])))
+            else:
+                ops.append(FilterOp(op=OP_CONST, type=t, ival=int(x[1])))
+        elif isinstance(x, bool):
+            ops.append(FilterOp(op=OP_CONST, type=BOOL, ival=int(x)))
+        elif isinstance(x, int):
+            ops.append(FilterOp(op=OP_CONST, type=INT if -2**31 <= x < 2**31 else LONG, ival=x))
+        elif isinstance(x, float):
+            ops.append(FilterOp(op=OP_CONST, type=DOUBLE, dval=x))
+        elif isinstance(x, str):  # a stream attribute of the representative event: the library refuses it
+            ops.append(FilterOp(op=OP_COL, col=spec.schema.col(x)))
+        else:
+            walk(x)
+
+    def walk(e):
+        head = e[0]
+        if head in CMP_OPS:
+            operand(e[1]); operand(e[2]); ops.append(FilterOp(op=CMP_OPS[head]))
+        elif head in ("and", "or"):  # (a bool group-by column is a condition by itself)
+            operand(e[1]); operand(e[2]); ops.append(FilterOp(op=OP_AND if head == "and" else OP_OR))
+        elif head == "not":
+            operand(e[1]); ops.append(FilterOp(op=OP_NOT))
+        else:
+            raise ValueError(f"bad having expression {e!r}")
+
+    if expr is not None:
+        walk(expr)
+    return ops
+
+
 @dataclass
 class QuerySpec:
     """`from S[filter]#window.kind(param...) select group..., aggs... group by group... insert ...`"""
@@ -178,6 +226,7 @@ class QuerySpec:
     start_attr: Optional[str] = None   # externalTimeBatch start time from this attribute
     timeout: Optional[int] = None      # externalTimeBatch(ts, T, start, timeout): scheduler timeout (ms)
     replace_ts: bool = False           # externalTimeBatch(..., timeout, true): replaceTimestampWithBatchEndTime
+    having: object = None              # `having` condition (compile_having syntax); batch windows, current output
     _keep: list = field(default_factory=list, repr=False)
 
     def desc(self) -> QueryDesc:
@@ -413,6 +462,9 @@ def setup_lib_prototypes(lib, prefix: str):
     lib.sh_query_set_ext_replace_ts.argtypes = [C.c_void_p, C.c_int32]
     lib.sh_query_set_compact_flushes.argtypes = [C.c_void_p, C.c_int32]
     lib.sh_query_set_device_flushes.argtypes = [C.c_void_p, C.c_int32]
+    if hasattr(lib, "sh_query_set_having"):  # (added without an ABI version change: found by symbol lookup)
+        lib.sh_query_set_having.argtypes = [C.c_void_p, P(FilterOp), C.c_int32]
+        lib.sh_having_check.argtypes = [P(QueryDesc), P(FilterOp), C.c_int32]
     lib.sh_query_rep_ts_attr.argtypes = [C.c_void_p, P(P(C.c_int64)), P(C.c_int64)]
     lib.sh_aggregation_timing.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sh_shard_flush_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -461,6 +513,7 @@ ABI_SYMBOLS = [
     "sh_aggregation_shard_create", "sh_aggregation_stats", "sh_stage", "sh_push_staged", "sh_ingest_stats",
     "sh_aggregation_find", "sh_aggregation_snapshot", "sh_aggregation_restore", "sh_query_set_output_rate", "sh_query_set_ext_timeout", "sh_query_set_ext_replace_ts", "sh_query_set_compact_flushes", "sh_query_set_device_flushes", "sh_query_rep_ts_attr", "sh_aggregation_timing", "sh_shard_flush_windows",
     "sh_shard_snapshot", "sh_shard_restore", "sh_query_set_strings", "sh_rate_apply_merged",
+    "sh_query_set_having", "sh_having_check",
 ]
 
 

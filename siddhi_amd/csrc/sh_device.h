@@ -527,4 +527,76 @@ struct WinCursor {
     }
 };
 
+// ---- aggregate folds (shared by sh_kernels.hip and sh_having_kernels.hip: one definition keeps the
+// double sums of both bit-identical) ------------------------------------------------------------------
+// value column j of an event held in registers (unrolled select: no dynamic register indexing)
+template <int V>
+__device__ __forceinline__ i64 pick(const i64 (&v)[V], int j) {
+    i64 x = v[0];
+#pragma unroll
+    for (int i = 1; i < V; i++) if (j == i) x = v[i];
+    return x;
+}
+
+// A key's aggregate fields held in registers while one of its events is folded, field j in register
+// slot j: the per-event updates driven by the per-field op table (sums: sum += x / value += (double) x;
+// min/max: replace when the state is new or x is smaller / larger in the column's type —
+// MinAttributeAggregatorExecutor `minValue > value`).
+// SIG != 0 is a compile-time op table (agg_sig): 4 bits per field, op + 1, so the folds of the common
+// plans carry no per-field dispatch.
+__host__ __device__ constexpr int sig_op(u32 sig, int j) { return (int)((sig >> (4 * j)) & 15u) - 1; }
+__host__ __device__ constexpr int sig_fields(u32 sig) { return sig == 0 ? 0 : 1 + sig_fields(sig >> 4); }
+constexpr u32 agg_sig3(int a, int b, int c) {
+    return (u32)(a + 1) | ((u32)(b + 1) << 4) | ((u32)(c + 1) << 8);
+}
+// the plan's op table as a signature (0 when it has no field or more than 4)
+inline u32 agg_sig(const AggPlan& ap) {
+    if (ap.n_fields < 1 || ap.n_fields > 4) return 0;
+    u32 s = 0;
+    for (int j = 0; j < ap.n_fields; j++) s |= (u32)(ap.fop[j] + 1) << (4 * j);
+    return s;
+}
+
+template <int V, int F = SH_MAX_AGGS, u32 SIG = 0>
+__device__ __forceinline__ void fold_fields(const AggPlan& ap, u64 (&f)[F], bool first, const i64 (&v)[V]) {
+#pragma unroll
+    for (int j = 0; j < F; j++) {
+        if (j >= (SIG ? sig_fields(SIG) : ap.n_fields)) break;
+        const int op = SIG ? sig_op(SIG, j) : ap.fop[j];
+        const i64 x = pick<V>(v, ap.fvcol[j]);
+        const u64 cur = f[j];
+        u64 r;
+        if (op <= FOP_ADD_DI) {
+            if (op == FOP_ADD_I) {
+                r = (u64)((first ? 0 : (i64)cur) + x);
+            } else {
+                double xd = op == FOP_ADD_DI ? (double)x : __longlong_as_double(x);
+                r = (u64)__double_as_longlong((first ? 0.0 : __longlong_as_double((i64)cur)) + xd);
+            }
+        } else {
+            bool lt, gt;  // x < cur, x > cur in the column's type (false on NaN, as in Java)
+            if (op <= FOP_MAX_I) {
+                lt = x < (i64)cur; gt = x > (i64)cur;
+            } else if (op <= FOP_MAX_D) {
+                double a = __longlong_as_double(x), b = __longlong_as_double((i64)cur);
+                lt = a < b; gt = a > b;
+            } else {
+                float a = (float)__longlong_as_double(x), b = (float)__longlong_as_double((i64)cur);
+                lt = a < b; gt = a > b;
+            }
+            const bool is_min = op == FOP_MIN_I || op == FOP_MIN_D || op == FOP_MIN_F;
+            r = (first || (is_min ? lt : gt)) ? (u64)x : cur;
+        }
+        f[j] = r;
+    }
+}
+
+// The output values of a row: count, avg = value / count, the other fields as folded.
+__device__ __forceinline__ u64 agg_out_kind(int k, u32 c, u64 fv) {
+    if (k == AK_COUNT) return (u64)(i64)c;
+    if (k == AK_AVG) return (u64)__double_as_longlong(__longlong_as_double((i64)fv) / (double)(i64)c);
+    return fv;
+}
+__device__ __forceinline__ u64 agg_out(const AggPlan& ap, int a, u32 c, u64 fv) { return agg_out_kind(ap.kind[a], c, fv); }
+
 }  // namespace shd

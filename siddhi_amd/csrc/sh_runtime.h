@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "sh_internal.h"
+#include "sh_having.h"
 
 struct sh_ctx {
     int device = 0;
@@ -298,6 +299,8 @@ struct sh_query {
     // sh_query_set_device_flushes: sh_push_device's flush layout stays in device memory (fl_dev)
     bool device_flushes = false;
     DevBuf fl_dev;
+    // sh_query_set_having: the program run_closed and sc_rows evaluate per event (sh_having.h)
+    HavingState hv;
     std::vector<std::pair<int64_t, int64_t>> xr_starts;
     std::vector<int64_t> xr_rep, xr_vals;
     bool xt_Lvalid = false;

@@ -442,8 +442,151 @@ static PosSrc pos_src(const sh_query* q, const sh_batch* b) {
 
 static int closed_finish(sh_query* q, bool host_out);
 
+// `having` on the plain batch windows (sh_having.h; QuerySelector.processInBatchGroupBy :315-374 keeps an
+// event only when the condition holds on the key's running aggregates): the stream.current.event
+// machinery with the chunk redefined — a row's chunk is its closed window, its flush clock that window's.
+// The push's passing events join the pending entries, the entries are sorted by (window, key slot), one
+// thread walks each run evaluating the program per event (k_hv_walk), and k_sc_emit / k_sc_flush_flags /
+// k_sc_flushes build rows and flushes: a window that keeps no row gives no flush. Synchronous: the rows
+// (device, or host for host_out) and the flush arrays (host) are complete on return.
+static int hv_closed(sh_query* q, const std::vector<Segment>& segs, const std::vector<int64_t>& clocks,
+                     const sh_batch* b, bool host_out) {
+    hipStream_t s = q->ctx->stream;
+    const int nk = q->kp.n, na = q->ap.n, nseg = (int)segs.size();
+    const int64_t n_old = q->n_pend;
+    const int64_t M = n_old + (b ? q->h_info->total_pass : 0);
+    PinnedVec<int64_t>& fo = host_out ? q->out.flush_offsets : q->dev_flush_offsets;
+    PinnedVec<int64_t>& fc = host_out ? q->out.flush_clock : q->dev_flush_clock;
+    if (fo.size() != 1) return sh_fail(SH_ERR_INVALID, "having: output appended twice in one call");
+    if (M <= 0) return SH_OK;
+    if (b && M > n_old) {
+        ColSet cs{};
+        cs.n = q->d.n_cols;
+        for (int c = 0; c < q->d.n_cols; c++) { cs.type[c] = q->load_type[c]; cs.ptr[c] = b->cols[c]; }
+        RCHK(grow_pending(q, M, n_old));
+        launch_compact_pending(s, b->ts, cs, pos_src(q, b), q->ap, 0, b->n, 0, n_old, q->blk_pass.as<int64_t>(),
+                               q->pend_pos.as<u32>(), q->pend_ts.as<int64_t>(), q->pend_vals.as<u64>(), q->pend_cap,
+                               nullptr, q->pend_gidx.as<u64>(), q->seq);
+        HIPCHK(hipGetLastError());
+    }
+    RCHK(q->h_up.reserve((size_t)nseg * sizeof(Segment)));
+    RCHK(q->segs.reserve(nseg * sizeof(Segment), false));
+    std::memcpy(q->h_up.p, segs.data(), (size_t)nseg * sizeof(Segment));
+    HIPCHK(hipMemcpyAsync(q->segs.p, q->h_up.p, nseg * sizeof(Segment), hipMemcpyHostToDevice, s));
+    RCHK(q->sc_h.reserve((size_t)nseg * 8 + 64));
+    RCHK(q->sc_bclk.reserve((size_t)nseg * 8, false));
+    std::memcpy(q->sc_h.p, clocks.data(), (size_t)nseg * 8);
+    HIPCHK(hipMemcpyAsync(q->sc_bclk.p, q->sc_h.p, (size_t)nseg * 8, hipMemcpyHostToDevice, s));
+    RCHK(q->sc_skey.reserve((size_t)M * 8, false));
+    RCHK(q->sc_skey2.reserve((size_t)M * 8, false));
+    RCHK(q->sc_idx.reserve((size_t)M * 4, false));
+    RCHK(q->sc_idx2.reserve((size_t)M * 4, false));
+    RCHK(q->sc_chunk.reserve((size_t)M * 8, false));
+    RCHK(q->sc_send.reserve((size_t)M * 8, false));
+    RCHK(q->sc_hd.reserve((size_t)(M + 1) * 4, false));
+    RCHK(q->sc_pos.reserve((size_t)(M + 1) * 4, false));
+    RCHK(q->sc_starts.reserve((size_t)(M + 1) * 4, false));
+    RCHK(q->sc_ghead.reserve((size_t)(M + 1) * 4, false));
+    RCHK(q->sc_pre.reserve((size_t)(M + 1) * 4, false));
+    RCHK(q->sc_slast.reserve((size_t)M * 4, false));
+    RCHK(q->sc_sval.reserve((size_t)std::max(na, 1) * M * 8, false));
+    RCHK(q->sc_tmp.reserve((size_t)((M + 1 + kTile - 1) / kTile + 16) * 8, false));
+    launch_hv_keys(s, M, n_old, q->seq, q->segs.as<Segment>(), nseg, q->pend_pos.as<u32>(), q->pend_gidx.as<u64>(),
+                   q->sc_skey.as<u64>(), q->sc_idx.as<u32>(), q->sc_chunk.as<int64_t>(), q->sc_send.as<int64_t>());
+    // the sorted keys are compared for equality alone: the window index (nseg = the window staying open)
+    // goes right above the slot bits (the slot mask + 1 of the sentinel key included) and the sort reads those
+    unsigned end_bit = 64, kb = 1, wb = 1;
+    while (kb < 33 && ((uint64_t)1 << kb) <= (uint64_t)q->kt.size_) kb++;
+    while (wb < 31 && ((int64_t)1 << wb) <= (int64_t)nseg) wb++;
+    if (kb <= 32 && kb + wb <= 48) {
+        launch_sc_pack_keys(s, M, kb, q->sc_skey.as<u64>());
+        end_bit = kb + wb;
+    }
+    size_t tb = 0;
+    if (sort_u64_pairs_bits(nullptr, &tb, nullptr, nullptr, nullptr, nullptr, M, end_bit, s))
+        return sh_fail(SH_ERR_DEVICE, "having: sort sizing");
+    RCHK(q->sc_sort.reserve(std::max<size_t>(tb, 16), false));
+    if (sort_u64_pairs_bits(q->sc_sort.p, &tb, q->sc_skey.as<u64>(), q->sc_skey2.as<u64>(), q->sc_idx.as<u32>(),
+                            q->sc_idx2.as<u32>(), M, end_bit, s))
+        return sh_fail(SH_ERR_DEVICE, "having: sort failed");
+    launch_rate_segments(s, M, q->sc_skey2.as<u64>(), q->sc_idx2.as<u32>(), 1, 0, q->sc_hd.as<u32>(),
+                         q->sc_pos.as<u32>(), q->sc_starts.as<u32>(), q->sc_tmp.as<int64_t>());
+    HIPCHK(hipMemsetAsync(q->sc_ghead.p, 0, (size_t)(M + 1) * 4, s));
+    HIPCHK(hipEventRecord(q->ev_agg0, s));
+    launch_hv_walk(s, q->hv.kind, M, q->sc_pos.as<u32>(), q->sc_starts.as<u32>(), q->sc_idx2.as<u32>(),
+                   q->sc_chunk.as<int64_t>(), q->pend_vals.as<u64>(), q->pend_cap, q->pend_pos.as<u32>(), q->ap,
+                   q->kt.dev(), q->kp, q->hv.prog, q->sc_ghead.as<u32>(), q->sc_sval.as<u64>(), q->sc_slast.as<u32>());
+    HIPCHK(hipEventRecord(q->ev_agg1, s));
+    // rows in output order: the heads scanned over every entry (a closed window's queued entries emit too)
+    HIPCHK(hipMemcpyAsync(q->sc_pre.p, q->sc_ghead.p, (size_t)(M + 1) * 4, hipMemcpyDeviceToDevice, s));
+    launch_scan_sum_large_u32(s, q->sc_pre.as<u32>(), M + 1, q->sc_tmp.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    RCHK(q->h_small_sc.reserve(64));
+    HIPCHK(hipMemcpyAsync(q->h_small_sc.p, q->sc_pre.as<uint32_t>() + M, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const int64_t T = *q->h_small_sc.as<uint32_t>();
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, q->ev_agg0, q->ev_agg1);
+    q->stats.main_kernel_ms += ms;
+    q->agg_bytes += M * (int64_t)(4 + 8 + 8 * q->ap.n_vcols) + T * (int64_t)(4 + 8 * na);
+    const int64_t TC = std::max<int64_t>(T, 1);
+    RCHK(q->out_ts.reserve(TC * 8, false));
+    RCHK(q->out_keys.reserve((size_t)std::max(1, nk) * TC * 8, false));
+    RCHK(q->out_vals.reserve((size_t)std::max(1, na) * TC * 8, false));
+    RCHK(q->out_nulls.reserve((size_t)std::max(1, na) * TC, false));
+    RCHK(q->out_expired.reserve(TC, false));
+    RCHK(q->out_rep.reserve(TC * 8, false));
+    RCHK(q->sc_ochunk.reserve(TC * 8, false));
+    RCHK(q->sc_osend.reserve(TC * 8, false));
+    HIPCHK(hipMemsetAsync(q->out_nulls.p, 0, q->out_nulls.cap, s));
+    HIPCHK(hipMemsetAsync(q->out_expired.p, 0, q->out_expired.cap, s));
+    q->zeroed_nulls = q->out_nulls.p;
+    q->zeroed_expired = q->out_expired.p;
+    if (!host_out) q->dev_out.n_rows = T;
+    if (T == 0) return SH_OK;
+    launch_sc_emit(s, M, 0, q->sc_ghead.as<u32>(), q->sc_pre.as<u32>(), q->sc_slast.as<u32>(), q->sc_sval.as<u64>(),
+                   q->pend_pos.as<u32>(), q->pend_ts.as<int64_t>(), q->pend_gidx.as<u64>(), q->sc_chunk.as<int64_t>(),
+                   q->sc_send.as<int64_t>(), q->kt.dev(), q->kp, na, T, q->out_ts.as<int64_t>(),
+                   q->out_keys.as<int64_t>(), q->out_vals.as<u64>(), q->out_rep.as<int64_t>(),
+                   q->sc_ochunk.as<int64_t>(), q->sc_osend.as<int64_t>(), nullptr);
+    // a flush ends where the row's window changes; its clock is the window's
+    RCHK(q->sc_fflag.reserve((size_t)(T + 1) * 4, false));
+    RCHK(q->sc_tmp.reserve((size_t)((T + 1 + kTile - 1) / kTile + 16) * 8, false));
+    launch_sc_flush_flags(s, T, q->sc_ochunk.as<int64_t>(), q->sc_fflag.as<u32>());
+    launch_scan_sum_large_u32(s, q->sc_fflag.as<u32>(), T + 1, q->sc_tmp.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(q->h_small_sc.p, q->sc_fflag.as<uint32_t>() + T, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const int64_t nf = *q->h_small_sc.as<uint32_t>();
+    RCHK(q->sc_fo.reserve((size_t)std::max<int64_t>(nf, 1) * 8, false));
+    RCHK(q->sc_fc.reserve((size_t)std::max<int64_t>(nf, 1) * 8, false));
+    launch_sc_flushes(s, T, q->sc_osend.as<int64_t>(), q->sc_fflag.as<u32>(), nullptr, 0, 0, q->sc_bclk.as<int64_t>(),
+                      q->sc_fo.as<int64_t>(), q->sc_fc.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    fo.resize((size_t)nf + 1);
+    fc.resize((size_t)nf);
+    HIPCHK(hipMemcpyAsync(fo.data() + 1, q->sc_fo.p, (size_t)nf * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(fc.data(), q->sc_fc.p, (size_t)nf * 8, hipMemcpyDeviceToHost, s));
+    if (host_out) {
+        OutHost& o = q->out;
+        o.ts.resize(T);
+        o.expired.assign(T, 0);
+        o.rep.resize(T);
+        o.keys.resize((size_t)nk * T);
+        o.vals.resize((size_t)na * T);
+        o.nulls.assign((size_t)na * T, 0);
+        HIPCHK(hipMemcpyAsync(o.ts.data(), q->out_ts.p, T * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(o.rep.data(), q->out_rep.p, T * 8, hipMemcpyDeviceToHost, s));
+        if (nk) HIPCHK(hipMemcpyAsync(o.keys.data(), q->out_keys.p, (size_t)nk * T * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(o.vals.data(), q->out_vals.p, (size_t)na * T * 8, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return SH_OK;
+}
+
 static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::vector<int64_t>& clocks,
                       const std::vector<int64_t>& windows, const sh_batch* b, bool host_out) {
+    if (q->hv.on) return hv_closed(q, segs, clocks, b, host_out);
     hipStream_t s = q->ctx->stream;
     int nseg = (int)segs.size();
     int64_t closed_hi = segs.back().hi;
@@ -692,7 +835,7 @@ static int closed_finish(sh_query* q, bool host_out) {
 // sh_query_set_device_flushes: a batch window's flush layout (built on the host: a few entries per
 // push) goes up to the device, so sh_push_device's whole output is in device memory
 int flush_layout_to_device(sh_query* q, sh_out& o) {
-    if (!q->device_flushes || q->rate.kind != SH_RATE_NONE || q->wide || !o.flush_offsets) return SH_OK;
+    if (!q->device_flushes || q->rate.kind != SH_RATE_NONE || q->wide || q->hv.on || !o.flush_offsets) return SH_OK;
     const size_t nf = (size_t)o.n_flushes;
     hipStream_t s = q->ctx->stream;
     RCHK(q->fl_dev.reserve((2 * nf + 1) * 8, false));
@@ -854,7 +997,9 @@ static int sc_rows(sh_query* q, const sh_batch* b, const std::vector<Bound>& bou
     const bool xt = q->d.expired_on && !per_event;  // timeBatch(T, true) with expired / all events
     // every new entry its own chunk (per-event sends, lengthBatch(L, true)): each is its own row, no head
     // flags, no scan of them, no chunk column and no read-back of the row count (current rows only)
-    const bool all_heads = !(xs || xt) && (per_event || (gv ? q->given_ss : ss) == 1);
+    // (a having program: a chunk's rows are the entries that pass, so the heads are always flagged and scanned)
+    const bool hv = q->hv.on;
+    const bool all_heads = !hv && !(xs || xt) && (per_event || (gv ? q->given_ss : ss) == 1);
     launch_sc_keys(s, M, n_old, q->sc_pcb.as<int64_t>(), nb, q->pend_pos.as<u32>(), q->pend_gidx.as<u64>(),
                    per_event ? 1 : 0, gv ? q->given_ss : ss, gv ? q->given_seq0 : seq0, q->sc_skey.as<u64>(),
                    q->sc_idx.as<u32>(), all_heads ? nullptr : q->sc_chunk.as<int64_t>(), q->sc_send.as<int64_t>(),
@@ -882,6 +1027,12 @@ static int sc_rows(sh_query* q, const sh_batch* b, const std::vector<Bound>& bou
                          q->sc_pos.as<u32>(), q->sc_starts.as<u32>(), q->sc_tmp.as<int64_t>());
     if (!all_heads) HIPCHK(hipMemsetAsync(q->sc_ghead.p, 0, (size_t)(M + 1) * 4, s));
     HIPCHK(hipEventRecord(q->ev_agg0, s));
+    if (hv)  // the program after every event of the push (sh_having.h): first / last passing entry per group
+        launch_hv_walk(s, q->hv.kind, M, q->sc_pos.as<u32>(), q->sc_starts.as<u32>(), q->sc_idx2.as<u32>(),
+                       q->sc_chunk.as<int64_t>(), q->pend_vals.as<u64>(), q->pend_cap, q->pend_pos.as<u32>(), q->ap,
+                       q->kt.dev(), q->kp, q->hv.prog, q->sc_ghead.as<u32>(), q->sc_sval.as<u64>(),
+                       q->sc_slast.as<u32>());
+    else
     launch_sc_walk(s, M, q->sc_hd.as<u32>(), q->sc_pos.as<u32>(), q->sc_starts.as<u32>(), q->sc_idx2.as<u32>(),
                    q->sc_chunk.as<int64_t>(), q->pend_vals.as<u64>(), q->pend_cap, q->ap, n_old,
                    all_heads ? nullptr : q->sc_ghead.as<u32>(),
@@ -1035,7 +1186,7 @@ static int sc_rows(sh_query* q, const sh_batch* b, const std::vector<Bound>& bou
             nf = *q->h_small_sc.as<uint32_t>();
         }
         q->compact_now = false;
-        const bool want_compact = q->compact_flushes && q->rate.kind == SH_RATE_NONE && !q->xmode && nf > 0 && nf == T;
+        const bool want_compact = q->compact_flushes && q->rate.kind == SH_RATE_NONE && !q->xmode && !hv && nf > 0 && nf == T;
         if (all_heads && want_compact) {
             // (a flush per row: check the rows' clocks against their timestamps before writing any flush)
             launch_sc_clock_is_ts(s, T, q->sc_osend.as<int64_t>(), q->sc_slp.as<int64_t>(), cv0 ? 1 : 0, clock0,
@@ -1381,6 +1532,7 @@ extern "C" int sh_query_set_ext_timeout(sh_query* q, int64_t ms) {
     if (q->seq != 0 || q->n_pend != 0 || q->clock_valid)
         return sh_fail(SH_ERR_INVALID, "sh_query_set_ext_timeout: set it before the first push");
     if (ms == 0) { q->xt_timeout = 0; return SH_OK; }
+    if (q->hv.on) return sh_fail(SH_ERR_UNSUPPORTED, "externalTimeBatch timeout with a having program");
     // partitioned: on the sorted partition lanes (lane 3), the Scheduler walked on the host (sh_plane.cpp
     // xt_walk) with its HashMap tie order, which hashes String.valueOf of the partition key
     const bool lanes = q->kind == 1 && q->d.partition_col >= 0 && q->sl && plane_is_sorted_lane(q);
@@ -2014,6 +2166,7 @@ extern "C" int sh_query_set_ext_replace_ts(sh_query* q, int32_t on) {
     if (q->seq != 0 || q->n_pend != 0 || q->clock_valid)
         return sh_fail(SH_ERR_INVALID, "sh_query_set_ext_replace_ts: set it before the first push");
     if (!on) { q->xt_replace = false; return SH_OK; }
+    if (q->hv.on) return sh_fail(SH_ERR_UNSUPPORTED, "replaceTimestampWithBatchEndTime with a having program");
     // unpartitioned, or partitioned on the sorted partition lanes (lane 3), whose rows carry the batch end
     const bool lanes = q->kind == 1 && q->d.partition_col >= 0 && q->sl && plane_is_sorted_lane(q);
     if ((q->kind != 0 && !lanes) || (q->d.partition_col >= 0 && !lanes) || q->given || q->internal_keys)

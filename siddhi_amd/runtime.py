@@ -84,6 +84,16 @@ def _check(rc: int):
         raise SiddhiError(rc, lib().sh_last_error().decode())
 
 
+def having_check(spec: abi.QuerySpec, expr=None) -> None:
+    """sh_having_check: raises SiddhiError with the library's verdict (SH_ERR_INVALID: malformed program,
+    SH_ERR_UNSUPPORTED: a shape that stays on the CPU) unless `spec` with its `having` condition (or `expr`)
+    runs on the GPU. Needs neither a context nor a GPU: what the shim calls at parse time."""
+    d = spec.desc()
+    ops = abi.compile_having(spec, spec.having if expr is None else expr)
+    arr = (abi.FilterOp * max(1, len(ops)))(*ops)
+    _check(lib().sh_having_check(C.byref(d), arr, len(ops)))
+
+
 class Context:
     def __init__(self, device: int = 0):
         self.h = C.c_void_p()
@@ -118,6 +128,8 @@ class GpuQuery:
         try:
             if spec.rate:
                 _check(lib().sh_query_set_output_rate(self.h, abi.RATE_KINDS[spec.rate[0]], int(spec.rate[1])))
+            if getattr(spec, "having", None) is not None:
+                self.set_having(spec.having)
             if spec.timeout:
                 _check(lib().sh_query_set_ext_timeout(self.h, int(spec.timeout)))
             if spec.replace_ts:
@@ -127,6 +139,13 @@ class GpuQuery:
         except Exception:
             self.close()
             raise
+
+    def set_having(self, expr):
+        """sh_query_set_having: the `having` condition (abi.compile_having syntax), evaluated after every event
+        on the key's running aggregates as QuerySelector.processInBatchGroupBy does. Once, before the first push."""
+        ops = abi.compile_having(self.spec, expr)
+        arr = (abi.FilterOp * max(1, len(ops)))(*ops)
+        _check(lib().sh_query_set_having(self.h, arr, len(ops)))
 
     def set_device_flushes(self, on: bool = True):
         """sh_query_set_device_flushes: sh_push_device leaves the flush layout in device memory too."""
