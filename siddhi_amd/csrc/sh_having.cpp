@@ -1,6 +1,6 @@
 // sh_having.cpp — the `having` program of a batch-window query: the type-checking compiler behind
 // sh_having_check and sh_query_set_having, and the per-query state (sh_having.h). The evaluation is in
-// sh_having_kernels.hip, routed from run_closed and sc_rows (sh_window.cpp).
+// sh_having_kernels.hip, routed from run_closed (sh_window.cpp) and sc_rows (sh_stream_current.cpp).
 #include "sh_having.h"
 
 #include <string>

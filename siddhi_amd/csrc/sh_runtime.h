@@ -413,7 +413,7 @@ struct sh_query {
     PinnedBuf x_h;
     std::vector<std::pair<int64_t, int64_t>> x_closes;  // (window start W, clock) seen by the call
     std::vector<int64_t> x_stamps;  // externalTimeBatch: attribute time (running max) closing flush j
-    // stream.current.event batch windows (sh_window.cpp sc_rows): scratch of a push
+    // stream.current.event batch windows (sh_stream_current.cpp): scratch of a push
     DevBuf sc_pcb, sc_skey, sc_skey2, sc_idx, sc_idx2, sc_chunk, sc_send, sc_hd, sc_pos, sc_starts, sc_tmp, sc_ghead,
         sc_pre, sc_sval, sc_slast, sc_ochunk, sc_osend, sc_sl, sc_sort, scx_fe, scx_fpre, scx_last, scx_rows, scx_rank,
         scx_clk;
@@ -489,6 +489,28 @@ int xout_finish(sh_query* q, bool host_out, const sh_out** out);
 // output rate limiting over a call's device output (sh_rate.cpp); flush_dev: the input's flush
 // arrays are device memory (sliding windows)
 int rate_apply(sh_query* q, const sh_out* in, bool flush_dev, bool host_out, const sh_out** out);
+
+// the flush layout a batch-window call fills: the host output's, or the device output's (host arrays too)
+struct FlushVecs {
+    PinnedVec<int64_t>& offsets;
+    PinnedVec<int64_t>& clocks;
+};
+inline FlushVecs flush_vecs(sh_query* q, bool host_out) {
+    if (host_out) return {q->out.flush_offsets, q->out.flush_clock};
+    return {q->dev_flush_offsets, q->dev_flush_clock};
+}
+
+// rows per event instead of per closed window (sh_stream_current.cpp): stream.current.event rows of a
+// push, the open window's keys as EXPIRED rows at a TIMER, `having` on the closed windows of a call
+int sc_rows(sh_query* q, const sh_batch* b, const std::vector<shd::Bound>& bounds, int64_t n_old, int64_t M, bool cv0,
+            int64_t clock0, int64_t seq0, bool host_out);
+int sc_expire_pending(sh_query* q, int64_t now, bool host_out);
+int hv_closed(sh_query* q, const std::vector<shd::Segment>& segs, const std::vector<int64_t>& clocks, const sh_batch* b,
+              bool host_out);
+// ... and what they need of sh_window.cpp: the push's passing events appended to the pending entries
+// [n_old, M); the closed windows' segment list on the device (q->segs)
+int append_pending(sh_query* q, const sh_batch* b, int64_t n_old, int64_t M);
+int upload_segments(sh_query* q, const std::vector<shd::Segment>& segs);
 
 // the filter restricted to partition key `key` (R12): base AND (pcol == key)
 int partition_filter(const FilterProg& base, int pcol, int ptype, int64_t key, FilterProg* out);

@@ -440,149 +440,56 @@ static PosSrc pos_src(const sh_query* q, const sh_batch* b) {
     return ps;
 }
 
-static int closed_finish(sh_query* q, bool host_out);
+// the batch's columns at the widths the kernels load them (b == NULL: a call without new events)
+static ColSet col_set(const sh_query* q, const sh_batch* b) {
+    ColSet cs{};
+    cs.n = q->d.n_cols;
+    for (int c = 0; c < q->d.n_cols; c++) { cs.type[c] = q->load_type[c]; cs.ptr[c] = b ? b->cols[c] : nullptr; }
+    return cs;
+}
 
-// `having` on the plain batch windows (sh_having.h; QuerySelector.processInBatchGroupBy :315-374 keeps an
-// event only when the condition holds on the key's running aggregates): the stream.current.event
-// machinery with the chunk redefined — a row's chunk is its closed window, its flush clock that window's.
-// The push's passing events join the pending entries, the entries are sorted by (window, key slot), one
-// thread walks each run evaluating the program per event (k_hv_walk), and k_sc_emit / k_sc_flush_flags /
-// k_sc_flushes build rows and flushes: a window that keeps no row gives no flush. Synchronous: the rows
-// (device, or host for host_out) and the flush arrays (host) are complete on return.
-static int hv_closed(sh_query* q, const std::vector<Segment>& segs, const std::vector<int64_t>& clocks,
-                     const sh_batch* b, bool host_out) {
-    hipStream_t s = q->ctx->stream;
-    const int nk = q->kp.n, na = q->ap.n, nseg = (int)segs.size();
-    const int64_t n_old = q->n_pend;
-    const int64_t M = n_old + (b ? q->h_info->total_pass : 0);
-    PinnedVec<int64_t>& fo = host_out ? q->out.flush_offsets : q->dev_flush_offsets;
-    PinnedVec<int64_t>& fc = host_out ? q->out.flush_clock : q->dev_flush_clock;
-    if (fo.size() != 1) return sh_fail(SH_ERR_INVALID, "having: output appended twice in one call");
-    if (M <= 0) return SH_OK;
-    if (b && M > n_old) {
-        ColSet cs{};
-        cs.n = q->d.n_cols;
-        for (int c = 0; c < q->d.n_cols; c++) { cs.type[c] = q->load_type[c]; cs.ptr[c] = b->cols[c]; }
-        RCHK(grow_pending(q, M, n_old));
-        launch_compact_pending(s, b->ts, cs, pos_src(q, b), q->ap, 0, b->n, 0, n_old, q->blk_pass.as<int64_t>(),
-                               q->pend_pos.as<u32>(), q->pend_ts.as<int64_t>(), q->pend_vals.as<u64>(), q->pend_cap,
-                               nullptr, q->pend_gidx.as<u64>(), q->seq);
-        HIPCHK(hipGetLastError());
-    }
-    RCHK(q->h_up.reserve((size_t)nseg * sizeof(Segment)));
-    RCHK(q->segs.reserve(nseg * sizeof(Segment), false));
-    std::memcpy(q->h_up.p, segs.data(), (size_t)nseg * sizeof(Segment));
-    HIPCHK(hipMemcpyAsync(q->segs.p, q->h_up.p, nseg * sizeof(Segment), hipMemcpyHostToDevice, s));
-    RCHK(q->sc_h.reserve((size_t)nseg * 8 + 64));
-    RCHK(q->sc_bclk.reserve((size_t)nseg * 8, false));
-    std::memcpy(q->sc_h.p, clocks.data(), (size_t)nseg * 8);
-    HIPCHK(hipMemcpyAsync(q->sc_bclk.p, q->sc_h.p, (size_t)nseg * 8, hipMemcpyHostToDevice, s));
-    RCHK(q->sc_skey.reserve((size_t)M * 8, false));
-    RCHK(q->sc_skey2.reserve((size_t)M * 8, false));
-    RCHK(q->sc_idx.reserve((size_t)M * 4, false));
-    RCHK(q->sc_idx2.reserve((size_t)M * 4, false));
-    RCHK(q->sc_chunk.reserve((size_t)M * 8, false));
-    RCHK(q->sc_send.reserve((size_t)M * 8, false));
-    RCHK(q->sc_hd.reserve((size_t)(M + 1) * 4, false));
-    RCHK(q->sc_pos.reserve((size_t)(M + 1) * 4, false));
-    RCHK(q->sc_starts.reserve((size_t)(M + 1) * 4, false));
-    RCHK(q->sc_ghead.reserve((size_t)(M + 1) * 4, false));
-    RCHK(q->sc_pre.reserve((size_t)(M + 1) * 4, false));
-    RCHK(q->sc_slast.reserve((size_t)M * 4, false));
-    RCHK(q->sc_sval.reserve((size_t)std::max(na, 1) * M * 8, false));
-    RCHK(q->sc_tmp.reserve((size_t)((M + 1 + kTile - 1) / kTile + 16) * 8, false));
-    launch_hv_keys(s, M, n_old, q->seq, q->segs.as<Segment>(), nseg, q->pend_pos.as<u32>(), q->pend_gidx.as<u64>(),
-                   q->sc_skey.as<u64>(), q->sc_idx.as<u32>(), q->sc_chunk.as<int64_t>(), q->sc_send.as<int64_t>());
-    // the sorted keys are compared for equality alone: the window index (nseg = the window staying open)
-    // goes right above the slot bits (the slot mask + 1 of the sentinel key included) and the sort reads those
-    unsigned end_bit = 64, kb = 1, wb = 1;
-    while (kb < 33 && ((uint64_t)1 << kb) <= (uint64_t)q->kt.size_) kb++;
-    while (wb < 31 && ((int64_t)1 << wb) <= (int64_t)nseg) wb++;
-    if (kb <= 32 && kb + wb <= 48) {
-        launch_sc_pack_keys(s, M, kb, q->sc_skey.as<u64>());
-        end_bit = kb + wb;
-    }
-    size_t tb = 0;
-    if (sort_u64_pairs_bits(nullptr, &tb, nullptr, nullptr, nullptr, nullptr, M, end_bit, s))
-        return sh_fail(SH_ERR_DEVICE, "having: sort sizing");
-    RCHK(q->sc_sort.reserve(std::max<size_t>(tb, 16), false));
-    if (sort_u64_pairs_bits(q->sc_sort.p, &tb, q->sc_skey.as<u64>(), q->sc_skey2.as<u64>(), q->sc_idx.as<u32>(),
-                            q->sc_idx2.as<u32>(), M, end_bit, s))
-        return sh_fail(SH_ERR_DEVICE, "having: sort failed");
-    launch_rate_segments(s, M, q->sc_skey2.as<u64>(), q->sc_idx2.as<u32>(), 1, 0, q->sc_hd.as<u32>(),
-                         q->sc_pos.as<u32>(), q->sc_starts.as<u32>(), q->sc_tmp.as<int64_t>());
-    HIPCHK(hipMemsetAsync(q->sc_ghead.p, 0, (size_t)(M + 1) * 4, s));
-    HIPCHK(hipEventRecord(q->ev_agg0, s));
-    launch_hv_walk(s, q->hv.kind, M, q->sc_pos.as<u32>(), q->sc_starts.as<u32>(), q->sc_idx2.as<u32>(),
-                   q->sc_chunk.as<int64_t>(), q->pend_vals.as<u64>(), q->pend_cap, q->pend_pos.as<u32>(), q->ap,
-                   q->kt.dev(), q->kp, q->hv.prog, q->sc_ghead.as<u32>(), q->sc_sval.as<u64>(), q->sc_slast.as<u32>());
-    HIPCHK(hipEventRecord(q->ev_agg1, s));
-    // rows in output order: the heads scanned over every entry (a closed window's queued entries emit too)
-    HIPCHK(hipMemcpyAsync(q->sc_pre.p, q->sc_ghead.p, (size_t)(M + 1) * 4, hipMemcpyDeviceToDevice, s));
-    launch_scan_sum_large_u32(s, q->sc_pre.as<u32>(), M + 1, q->sc_tmp.as<int64_t>());
-    HIPCHK(hipGetLastError());
-    RCHK(q->h_small_sc.reserve(64));
-    HIPCHK(hipMemcpyAsync(q->h_small_sc.p, q->sc_pre.as<uint32_t>() + M, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    const int64_t T = *q->h_small_sc.as<uint32_t>();
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, q->ev_agg0, q->ev_agg1);
-    q->stats.main_kernel_ms += ms;
-    q->agg_bytes += M * (int64_t)(4 + 8 + 8 * q->ap.n_vcols) + T * (int64_t)(4 + 8 * na);
-    const int64_t TC = std::max<int64_t>(T, 1);
-    RCHK(q->out_ts.reserve(TC * 8, false));
-    RCHK(q->out_keys.reserve((size_t)std::max(1, nk) * TC * 8, false));
-    RCHK(q->out_vals.reserve((size_t)std::max(1, na) * TC * 8, false));
-    RCHK(q->out_nulls.reserve((size_t)std::max(1, na) * TC, false));
-    RCHK(q->out_expired.reserve(TC, false));
-    RCHK(q->out_rep.reserve(TC * 8, false));
-    RCHK(q->sc_ochunk.reserve(TC * 8, false));
-    RCHK(q->sc_osend.reserve(TC * 8, false));
-    HIPCHK(hipMemsetAsync(q->out_nulls.p, 0, q->out_nulls.cap, s));
-    HIPCHK(hipMemsetAsync(q->out_expired.p, 0, q->out_expired.cap, s));
-    q->zeroed_nulls = q->out_nulls.p;
-    q->zeroed_expired = q->out_expired.p;
-    if (!host_out) q->dev_out.n_rows = T;
-    if (T == 0) return SH_OK;
-    launch_sc_emit(s, M, 0, q->sc_ghead.as<u32>(), q->sc_pre.as<u32>(), q->sc_slast.as<u32>(), q->sc_sval.as<u64>(),
-                   q->pend_pos.as<u32>(), q->pend_ts.as<int64_t>(), q->pend_gidx.as<u64>(), q->sc_chunk.as<int64_t>(),
-                   q->sc_send.as<int64_t>(), q->kt.dev(), q->kp, na, T, q->out_ts.as<int64_t>(),
-                   q->out_keys.as<int64_t>(), q->out_vals.as<u64>(), q->out_rep.as<int64_t>(),
-                   q->sc_ochunk.as<int64_t>(), q->sc_osend.as<int64_t>(), nullptr);
-    // a flush ends where the row's window changes; its clock is the window's
-    RCHK(q->sc_fflag.reserve((size_t)(T + 1) * 4, false));
-    RCHK(q->sc_tmp.reserve((size_t)((T + 1 + kTile - 1) / kTile + 16) * 8, false));
-    launch_sc_flush_flags(s, T, q->sc_ochunk.as<int64_t>(), q->sc_fflag.as<u32>());
-    launch_scan_sum_large_u32(s, q->sc_fflag.as<u32>(), T + 1, q->sc_tmp.as<int64_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(q->h_small_sc.p, q->sc_fflag.as<uint32_t>() + T, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    const int64_t nf = *q->h_small_sc.as<uint32_t>();
-    RCHK(q->sc_fo.reserve((size_t)std::max<int64_t>(nf, 1) * 8, false));
-    RCHK(q->sc_fc.reserve((size_t)std::max<int64_t>(nf, 1) * 8, false));
-    launch_sc_flushes(s, T, q->sc_osend.as<int64_t>(), q->sc_fflag.as<u32>(), nullptr, 0, 0, q->sc_bclk.as<int64_t>(),
-                      q->sc_fo.as<int64_t>(), q->sc_fc.as<int64_t>());
-    HIPCHK(hipGetLastError());
-    fo.resize((size_t)nf + 1);
-    fc.resize((size_t)nf);
-    HIPCHK(hipMemcpyAsync(fo.data() + 1, q->sc_fo.p, (size_t)nf * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(fc.data(), q->sc_fc.p, (size_t)nf * 8, hipMemcpyDeviceToHost, s));
-    if (host_out) {
-        OutHost& o = q->out;
-        o.ts.resize(T);
-        o.expired.assign(T, 0);
-        o.rep.resize(T);
-        o.keys.resize((size_t)nk * T);
-        o.vals.resize((size_t)na * T);
-        o.nulls.assign((size_t)na * T, 0);
-        HIPCHK(hipMemcpyAsync(o.ts.data(), q->out_ts.p, T * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(o.rep.data(), q->out_rep.p, T * 8, hipMemcpyDeviceToHost, s));
-        if (nk) HIPCHK(hipMemcpyAsync(o.keys.data(), q->out_keys.p, (size_t)nk * T * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(o.vals.data(), q->out_vals.p, (size_t)na * T * 8, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
+// the window and clock state a push of N events in sends of `send_size` starts from
+static WinParams base_win_params(const sh_query* q, int64_t send_size, int64_t N) {
+    WinParams wp{};
+    wp.kind = q->d.window;
+    wp.e0_valid = q->e0_valid;
+    wp.clock_valid = q->clock_valid;
+    wp.L = wp.T = q->d.window_param;
+    wp.cal = q->cal;
+    wp.cal_tz = q->cal_tz;
+    wp.E0 = q->E0;
+    wp.clock0 = q->clock;
+    wp.W_open = q->W_open;
+    wp.n_pend = q->n_pend;
+    wp.send_size = send_size;
+    wp.N = N;
+    return wp;
+}
+
+// the segment list goes up from pinned memory (an async copy from pageable memory may read it after
+// the caller returned)
+int upload_segments(sh_query* q, const std::vector<Segment>& segs) {
+    const size_t bytes = segs.size() * sizeof(Segment);
+    RCHK(q->h_up.reserve(bytes));
+    RCHK(q->segs.reserve(bytes, false));
+    std::memcpy(q->h_up.p, segs.data(), bytes);
+    HIPCHK(hipMemcpyAsync(q->segs.p, q->h_up.p, bytes, hipMemcpyHostToDevice, q->ctx->stream));
     return SH_OK;
 }
+
+// every passing event of the push joins the pending entries, as [n_old, M) (a sharded owner's with
+// their global indices; sh_query_set_having refuses an owner, so hv_closed never has any)
+int append_pending(sh_query* q, const sh_batch* b, int64_t n_old, int64_t M) {
+    RCHK(grow_pending(q, M, n_old));
+    launch_compact_pending(q->ctx->stream, b->ts, col_set(q, b), pos_src(q, b), q->ap, 0, b->n, 0, n_old,
+                           q->blk_pass.as<int64_t>(), q->pend_pos.as<u32>(), q->pend_ts.as<int64_t>(),
+                           q->pend_vals.as<u64>(), q->pend_cap, q->given ? q->given_gidx : nullptr,
+                           q->pend_gidx.as<u64>(), q->seq);
+    HIPCHK(hipGetLastError());
+    return SH_OK;
+}
+
+static int closed_finish(sh_query* q, bool host_out);
 
 static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::vector<int64_t>& clocks,
                       const std::vector<int64_t>& windows, const sh_batch* b, bool host_out) {
@@ -590,9 +497,7 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
     hipStream_t s = q->ctx->stream;
     int nseg = (int)segs.size();
     int64_t closed_hi = segs.back().hi;
-    ColSet cs{};
-    cs.n = q->d.n_cols;
-    for (int c = 0; c < q->d.n_cols; c++) { cs.type[c] = q->load_type[c]; cs.ptr[c] = b ? b->cols[c] : nullptr; }
+    const ColSet cs = col_set(q, b);
     const int64_t* ts = b ? b->ts : nullptr;
     if (q->ap.n == 0) {
         // pass-through (`select *` without aggregators or group-by): every passing event of the
@@ -600,10 +505,7 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
         RCHK(q->pass_pos.reserve((size_t)(closed_hi + 1) * 4, false));
         RCHK(q->x_tmp.reserve((size_t)((closed_hi + 1 + kTile - 1) / kTile + 16) * 8, false));
         RCHK(q->counters.reserve(64 + (size_t)nseg * 4, false));
-        RCHK(q->h_up.reserve((size_t)nseg * sizeof(Segment)));
-        RCHK(q->segs.reserve(nseg * sizeof(Segment), false));
-        std::memcpy(q->h_up.p, segs.data(), (size_t)nseg * sizeof(Segment));
-        HIPCHK(hipMemcpyAsync(q->segs.p, q->h_up.p, nseg * sizeof(Segment), hipMemcpyHostToDevice, s));
+        RCHK(upload_segments(q, segs));
         const int64_t cap = std::max<int64_t>(closed_hi, 1);
         RCHK(q->out_ts.reserve(cap * 8, false));
         RCHK(q->out_rep.reserve(cap * 8, false));
@@ -655,17 +557,8 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
     RCHK(q->counters.reserve(64 + (size_t)n_units * 4, false));
     uint32_t* unit_rows = (uint32_t*)(q->counters.as<char>() + 64);  // written by every unit's workgroup
     HIPCHK(hipMemsetAsync(q->first_bits.p, 0, (size_t)n_words * 4, s));
-    // the segment list goes up from pinned memory (an async copy from pageable memory may read it
-    // after this function returned)
-    RCHK(q->h_up.reserve((size_t)nseg * sizeof(Segment)));
-    RCHK(q->segs.reserve(nseg * sizeof(Segment), false));
-    std::memcpy(q->h_up.p, segs.data(), (size_t)nseg * sizeof(Segment));
-    HIPCHK(hipMemcpyAsync(q->segs.p, q->h_up.p, nseg * sizeof(Segment), hipMemcpyHostToDevice, s));
+    RCHK(upload_segments(q, segs));
     const Segment* dsegs = q->segs.as<Segment>();
-    // One flat workgroup per segment walks every event of the segment, passing or not, and
-    // serialises a key's events in conflict rounds: fine for short batches of few keys. Key
-    // partitions, long windows and sparse partitions (R12 keeps one partition) take the compacting
-    // multisplit (usually launched already by push_core) and the thread-ownership kernel.
     SH_TRACE("run_closed nseg=%d closed_hi=%lld row_cap=%lld own=%d P=%d NL=%d ms_ready=%d", nseg, (long long)closed_hi,
              (long long)row_cap, (int)own, q->P, q->NL, (int)q->ms_ready);
     if (own) {
@@ -718,12 +611,12 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
                            q->pend_gidx.as<u64>(), q->given && b ? q->given_gidx : nullptr,
                            q->given ? q->out_order.as<int64_t>() : nullptr, q->seq, q->out_rep.as<int64_t>());
     else
-    launch_emit_rows(s, q->rows.as<u64>(), RW, unit_rows, n_units, unit_stride, cap, q->counters.as<u32>(),
-                     q->word_pre.as<u64>(), na, q->kt.dev(), q->kp, q->n_pend,
-                     q->pend_ts.as<int64_t>(), ts, cap,
-                     q->out_ts.as<int64_t>(), q->out_keys.as<int64_t>(), q->out_vals.as<u64>(), q->pend_gidx.as<u64>(),
-                     q->given && b ? q->given_gidx : nullptr, q->given ? q->out_order.as<int64_t>() : nullptr, q->seq,
-                     q->out_rep.as<int64_t>(), q->emit_stage.as<u64>());
+        launch_emit_rows(s, q->rows.as<u64>(), RW, unit_rows, n_units, unit_stride, cap, q->counters.as<u32>(),
+                         q->word_pre.as<u64>(), na, q->kt.dev(), q->kp, q->n_pend,
+                         q->pend_ts.as<int64_t>(), ts, cap,
+                         q->out_ts.as<int64_t>(), q->out_keys.as<int64_t>(), q->out_vals.as<u64>(), q->pend_gidx.as<u64>(),
+                         q->given && b ? q->given_gidx : nullptr, q->given ? q->out_order.as<int64_t>() : nullptr, q->seq,
+                         q->out_rep.as<int64_t>(), q->emit_stage.as<u64>());
     // batch-window rows always have a value (count >= 1) and are CURRENT events: the null and
     // expired flags are zeroed once per buffer, nothing here ever sets them
     if (q->out_nulls.p != q->zeroed_nulls) {
@@ -818,18 +711,38 @@ static int closed_finish(sh_query* q, bool host_out) {
         }
     }
     // flush bookkeeping (one flush per non-empty closed segment)
-    PinnedVec<int64_t>& fo = host_out ? q->out.flush_offsets : q->dev_flush_offsets;
-    PinnedVec<int64_t>& fc = host_out ? q->out.flush_clock : q->dev_flush_clock;
-    int64_t acc = fo.back();
+    const FlushVecs fl = flush_vecs(q, host_out);
+    int64_t acc = fl.offsets.back();
     for (int i = 0; i < t.nseg; i++) {
         if (seg_rows[i] == 0) continue;
         acc += seg_rows[i];
-        fo.push_back(acc);
-        fc.push_back(t.clocks[i]);
+        fl.offsets.push_back(acc);
+        fl.clocks.push_back(t.clocks[i]);
         q->flush_window.push_back(t.windows[i]);
     }
     if (!host_out) q->dev_out.n_rows = n_rows;
     return SH_OK;
+}
+
+// The open window's events aggregated as one closed window at `clock`, rows and flush complete on
+// return. They stay queued: a caller that closes the window for good clears n_pend itself (closed_finish
+// reads the tail run_closed left, not n_pend, so before or after makes no difference).
+static int close_open_window(sh_query* q, int64_t clock, bool host_out) {
+    std::vector<Segment> segs{Segment{0, q->n_pend}};
+    std::vector<int64_t> clocks{clock}, windows{q->W_open};
+    RCHK(run_closed(q, segs, clocks, windows, nullptr, host_out));
+    HIPCHK(hipStreamSynchronize(q->ctx->stream));
+    return closed_finish(q, host_out);
+}
+
+// what every call starts from: no flush, no device rows, no split or closed windows left by the last call
+static void reset_call_output(sh_query* q) {
+    q->dev_flush_offsets.assign(1, 0);
+    q->dev_flush_clock.clear();
+    q->flush_window.clear();
+    q->dev_out = sh_out{};
+    q->ms_ready = false;
+    q->tail.active = false;
 }
 
 // sh_query_set_device_flushes: a batch window's flush layout (built on the host: a few entries per
@@ -847,7 +760,7 @@ int flush_layout_to_device(sh_query* q, sh_out& o) {
     return SH_OK;
 }
 
-static void finish_out(sh_query* q, bool host_out, const sh_out** out) {
+static int finish_out(sh_query* q, bool host_out, const sh_out** out) {
     const bool compact = q->compact_now;
     q->compact_now = false;
     if (host_out) {
@@ -866,7 +779,7 @@ static void finish_out(sh_query* q, bool host_out, const sh_out** out) {
         for (int i = 0; i < q->ap.n; i++) o.val_types[i] = q->vtypes[i];
         o.flush_offsets = compact ? nullptr : q->dev_flush_offsets.data();
         o.flush_clock = compact ? nullptr : q->dev_flush_clock.data();
-        if (!compact) (void)flush_layout_to_device(q, o);
+        if (!compact) RCHK(flush_layout_to_device(q, o));
         o.ts = q->out_ts.as<int64_t>();
         o.expired = q->out_expired.as<uint8_t>();
         o.keys = q->out_keys.as<int64_t>();
@@ -875,6 +788,7 @@ static void finish_out(sh_query* q, bool host_out, const sh_out** out) {
         o.rep = q->out_rep.as<int64_t>();
         *out = &o;
     }
+    return SH_OK;
 }
 
 // Partitioned timeBatch (`partition with (pcol of S)`): TimeBatchWindowProcessor.nextEmitTime is a
@@ -959,407 +873,6 @@ int query_resize_for_restore(sh_query* q, size_t table_size, int64_t n_pend, con
     return grow_pending(q, n_pend, 0);
 }
 
-// stream.current.event batch windows (LengthBatchWindowProcessor.processStreamCurrentEvents :245-274,
-// TimeBatchWindowProcessor RESET mode :262-340): the pending entries [0, n_old) are the open window's
-// earlier events, [n_old, M) this push's passing events (sh_kernels.hip k_sc_*). One flush per chunk:
-// every passing event for lengthBatch (:160-182 sends each event's chunk on its own), every send with
-// passing events for timeBatch; the flush clock is the send's playback clock.
-static int sc_rows(sh_query* q, const sh_batch* b, const std::vector<Bound>& bounds, int64_t n_old, int64_t M,
-                   bool cv0, int64_t clock0, int64_t seq0, bool host_out) {
-    hipStream_t s = q->ctx->stream;
-    const int nk = q->kp.n, na = q->ap.n;
-    const int nb = (int)bounds.size();
-    const bool per_event = q->d.window == SH_WIN_LENGTH_BATCH;
-    const int64_t N = b->n, ss = b->send_size;
-    const int64_t n_sends = ss > 0 ? (N + ss - 1) / ss : 1;
-    RCHK(q->sc_hp.reserve((size_t)std::max(nb, 1) * 8 + 64));
-    for (int i = 0; i < nb; i++) q->sc_hp.as<int64_t>()[i] = bounds[i].pcb;
-    RCHK(q->sc_pcb.reserve((size_t)std::max(nb, 1) * 8, false));
-    if (nb) HIPCHK(hipMemcpyAsync(q->sc_pcb.p, q->sc_hp.p, (size_t)nb * 8, hipMemcpyHostToDevice, s));
-    RCHK(q->sc_skey.reserve((size_t)M * 8, false));
-    RCHK(q->sc_skey2.reserve((size_t)M * 8, false));
-    RCHK(q->sc_idx.reserve((size_t)M * 4, false));
-    RCHK(q->sc_idx2.reserve((size_t)M * 4, false));
-    RCHK(q->sc_chunk.reserve((size_t)M * 8, false));
-    RCHK(q->sc_send.reserve((size_t)M * 8, false));
-    RCHK(q->sc_hd.reserve((size_t)(M + 1) * 4, false));
-    RCHK(q->sc_pos.reserve((size_t)(M + 1) * 4, false));
-    RCHK(q->sc_starts.reserve((size_t)(M + 1) * 4, false));
-    RCHK(q->sc_ghead.reserve((size_t)(M + 1) * 4, false));
-    RCHK(q->sc_pre.reserve((size_t)(M + 1) * 4, false));
-    RCHK(q->sc_slast.reserve((size_t)M * 4, false));
-    RCHK(q->sc_sval.reserve((size_t)std::max(na, 1) * M * 8, false));
-    RCHK(q->sc_tmp.reserve((size_t)((M + 1 + kTile - 1) / kTile + 16) * 8, false));
-    RCHK(q->sc_sl.reserve((size_t)n_sends * 8, false));
-    // (a sharded owner: records are one send each for their clocks, chunks are the global sends)
-    const bool gv = q->given_clk != nullptr;
-    const bool xs = q->d.expired_on && per_event;   // lengthBatch(L, true) with expired / all events
-    const bool xt = q->d.expired_on && !per_event;  // timeBatch(T, true) with expired / all events
-    // every new entry its own chunk (per-event sends, lengthBatch(L, true)): each is its own row, no head
-    // flags, no scan of them, no chunk column and no read-back of the row count (current rows only)
-    // (a having program: a chunk's rows are the entries that pass, so the heads are always flagged and scanned)
-    const bool hv = q->hv.on;
-    const bool all_heads = !hv && !(xs || xt) && (per_event || (gv ? q->given_ss : ss) == 1);
-    launch_sc_keys(s, M, n_old, q->sc_pcb.as<int64_t>(), nb, q->pend_pos.as<u32>(), q->pend_gidx.as<u64>(),
-                   per_event ? 1 : 0, gv ? q->given_ss : ss, gv ? q->given_seq0 : seq0, q->sc_skey.as<u64>(),
-                   q->sc_idx.as<u32>(), all_heads ? nullptr : q->sc_chunk.as<int64_t>(), q->sc_send.as<int64_t>(),
-                   gv ? 1 : 0);
-    // current rows only: the sorted keys are compared for equality alone, so the window index goes right
-    // above the slot bits and the radix sort reads those bits only (C2: 24 of 64)
-    unsigned end_bit = 64;
-    if (!(xs || xt)) {
-        unsigned kb = 1, wb = 1;
-        while (kb < 32 && ((uint64_t)1 << kb) < (uint64_t)q->kt.size_) kb++;
-        while (wb < 31 && ((int64_t)1 << wb) <= (int64_t)nb) wb++;
-        if (kb + wb <= 48) {
-            launch_sc_pack_keys(s, M, kb, q->sc_skey.as<u64>());
-            end_bit = kb + wb;
-        }
-    }
-    size_t tb = 0;
-    if (sort_u64_pairs_bits(nullptr, &tb, nullptr, nullptr, nullptr, nullptr, M, end_bit, s))
-        return sh_fail(SH_ERR_DEVICE, "stream.current: sort sizing");
-    RCHK(q->sc_sort.reserve(std::max<size_t>(tb, 16), false));
-    if (sort_u64_pairs_bits(q->sc_sort.p, &tb, q->sc_skey.as<u64>(), q->sc_skey2.as<u64>(), q->sc_idx.as<u32>(),
-                            q->sc_idx2.as<u32>(), M, end_bit, s))
-        return sh_fail(SH_ERR_DEVICE, "stream.current: sort failed");
-    launch_rate_segments(s, M, q->sc_skey2.as<u64>(), q->sc_idx2.as<u32>(), 1, 0, q->sc_hd.as<u32>(),
-                         q->sc_pos.as<u32>(), q->sc_starts.as<u32>(), q->sc_tmp.as<int64_t>());
-    if (!all_heads) HIPCHK(hipMemsetAsync(q->sc_ghead.p, 0, (size_t)(M + 1) * 4, s));
-    HIPCHK(hipEventRecord(q->ev_agg0, s));
-    if (hv)  // the program after every event of the push (sh_having.h): first / last passing entry per group
-        launch_hv_walk(s, q->hv.kind, M, q->sc_pos.as<u32>(), q->sc_starts.as<u32>(), q->sc_idx2.as<u32>(),
-                       q->sc_chunk.as<int64_t>(), q->pend_vals.as<u64>(), q->pend_cap, q->pend_pos.as<u32>(), q->ap,
-                       q->kt.dev(), q->kp, q->hv.prog, q->sc_ghead.as<u32>(), q->sc_sval.as<u64>(),
-                       q->sc_slast.as<u32>());
-    else
-    launch_sc_walk(s, M, q->sc_hd.as<u32>(), q->sc_pos.as<u32>(), q->sc_starts.as<u32>(), q->sc_idx2.as<u32>(),
-                   q->sc_chunk.as<int64_t>(), q->pend_vals.as<u64>(), q->pend_cap, q->ap, n_old,
-                   all_heads ? nullptr : q->sc_ghead.as<u32>(),
-                   q->sc_sval.as<u64>(), q->sc_slast.as<u32>());
-    HIPCHK(hipEventRecord(q->ev_agg1, s));
-    const int64_t nn = M - n_old;
-    // the sends' playback clocks: TimestampGeneratorImpl only moves forward (prefix max of send-last ts);
-    // a sharded owner's records (one send each) carry their global send's clock instead
-    if (q->given_clk) {
-        if (ss != 1) return sh_fail(SH_ERR_INVALID, "sharded stream.current: records are one send each");
-        cv0 = false;  // (the records' clocks are whole; the owner's clock is already the push's end clock)
-        HIPCHK(hipMemcpyAsync(q->sc_sl.p, q->given_clk, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
-    } else {
-        launch_sc_send_last(s, b->ts, N, ss, n_sends, q->sc_sl.as<int64_t>());
-    }
-    HIPCHK(hipGetLastError());
-    // (host scratch kept by the query: a fresh 8-byte-per-send vector per push faulted in its pages —
-    // hundreds of MB per C2-sized push)
-    std::vector<int64_t>& sl = q->sc_sl_host;
-    if (xs || xt) {
-        RCHK(q->sc_h.reserve((size_t)n_sends * 8 + 64));
-        HIPCHK(hipMemcpyAsync(q->sc_h.p, q->sc_sl.p, (size_t)n_sends * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        sl.resize((size_t)n_sends);
-        const int64_t* hs = q->sc_h.as<int64_t>();
-        bool cv = cv0;
-        int64_t c = clock0;
-        for (int64_t i = 0; i < n_sends; i++) {
-            c = cv ? std::max(c, hs[i]) : hs[i];
-            cv = true;
-            sl[i] = c;
-        }
-    } else {
-        // current rows only: the sends' clocks stay on the device (the flushes are built there too)
-        size_t stb = 0;
-        RCHK(q->sc_slp.reserve((size_t)n_sends * 8, false));
-        if (scan_max_i64(nullptr, &stb, q->sc_sl.as<int64_t>(), q->sc_slp.as<int64_t>(), n_sends, s))
-            return sh_fail(SH_ERR_DEVICE, "stream.current: scan sizing");
-        RCHK(q->sc_sort.reserve(std::max<size_t>(stb, 16), false));
-        if (scan_max_i64(q->sc_sort.p, &stb, q->sc_sl.as<int64_t>(), q->sc_slp.as<int64_t>(), n_sends, s))
-            return sh_fail(SH_ERR_DEVICE, "stream.current: scan failed");
-    }
-    const int cur_on = q->d.current_on ? 1 : 0;
-    int64_t T = 0;
-    if (xs || xt) {
-        RCHK(q->scx_fe.reserve((size_t)(M + 1) * 4, false));
-        RCHK(q->scx_fpre.reserve((size_t)(M + 1) * 4, false));
-        RCHK(q->scx_last.reserve((size_t)M * 4, false));
-        RCHK(q->scx_rows.reserve((size_t)(nn + 2) * 4, false));
-        RCHK(q->scx_rank.reserve((size_t)std::max<int64_t>(nn, 1) * 8, false));
-        RCHK(q->scx_clk.reserve((size_t)n_sends * 8, false));
-        HIPCHK(hipMemsetAsync(q->scx_fe.p, 0, (size_t)(M + 1) * 4, s));
-        launch_scx_first(s, M, q->sc_hd.as<u32>(), q->sc_pos.as<u32>(), q->sc_starts.as<u32>(), q->sc_idx2.as<u32>(),
-                         q->scx_fe.as<u32>(), q->scx_fpre.as<u32>(), q->scx_last.as<u32>());
-        HIPCHK(hipMemcpyAsync(q->scx_fpre.p, q->scx_fe.p, (size_t)(M + 1) * 4, hipMemcpyDeviceToDevice, s));
-        launch_scan_sum_large_u32(s, q->scx_fpre.as<u32>(), M + 1, q->sc_tmp.as<int64_t>());
-        if (xs)
-            launch_scx_count(s, M, n_old, q->sc_pcb.as<int64_t>(), q->sc_skey.as<u64>(), q->sc_skey2.as<u64>(),
-                             q->sc_idx2.as<u32>(), q->scx_fpre.as<u32>(), cur_on, 1, q->scx_rows.as<u32>(),
-                             q->scx_rank.as<int64_t>());
-        else
-            launch_scxt_count(s, M, n_old, q->sc_pcb.as<int64_t>(), nb, q->sc_skey.as<u64>(), q->scx_fpre.as<u32>(),
-                              q->sc_ghead.as<u32>(), cur_on, q->scx_rows.as<u32>());
-        const int64_t nr = xs ? nn + 1 : nn + 2;  // (timeBatch: rows[nn] = windows closing after the last entry)
-        launch_scan_sum_large_u32(s, q->scx_rows.as<u32>(), nr, q->sc_tmp.as<int64_t>());
-        if (xs) {
-            std::memcpy(q->sc_h.p, sl.data(), (size_t)n_sends * 8);
-            HIPCHK(hipMemcpyAsync(q->scx_clk.p, q->sc_h.p, (size_t)n_sends * 8, hipMemcpyHostToDevice, s));
-        } else {  // timeBatch: the clock of each window start (the TIMER chunk's clock)
-            RCHK(q->scx_clk.reserve((size_t)std::max(nb, 1) * 8, false));
-            RCHK(q->sc_h.reserve((size_t)std::max<int64_t>(nb, n_sends) * 8 + 64));
-            for (int i = 0; i < nb; i++) q->sc_h.as<int64_t>()[i] = bounds[i].clock;
-            if (nb) HIPCHK(hipMemcpyAsync(q->scx_clk.p, q->sc_h.p, (size_t)nb * 8, hipMemcpyHostToDevice, s));
-        }
-        HIPCHK(hipGetLastError());
-        RCHK(q->h_small_sc.reserve(64));
-        HIPCHK(hipMemcpyAsync(q->h_small_sc.p, q->scx_rows.as<uint32_t>() + nr - 1, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        T = *q->h_small_sc.as<uint32_t>();
-    } else if (all_heads) {
-        T = nn;
-    } else {
-        HIPCHK(hipMemcpyAsync(q->sc_pre.p, q->sc_ghead.as<uint32_t>() + n_old, (size_t)(nn + 1) * 4,
-                              hipMemcpyDeviceToDevice, s));
-        launch_scan_sum_large_u32(s, q->sc_pre.as<u32>(), nn + 1, q->sc_tmp.as<int64_t>());
-        HIPCHK(hipGetLastError());
-        RCHK(q->h_small_sc.reserve(64));
-        HIPCHK(hipMemcpyAsync(q->h_small_sc.p, q->sc_pre.as<uint32_t>() + nn, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        T = *q->h_small_sc.as<uint32_t>();
-    }
-    const int64_t TC = std::max<int64_t>(T, 1);
-    RCHK(q->out_ts.reserve(TC * 8, false));
-    RCHK(q->out_keys.reserve((size_t)std::max(1, nk) * TC * 8, false));
-    RCHK(q->out_vals.reserve((size_t)std::max(1, na) * TC * 8, false));
-    RCHK(q->out_nulls.reserve((size_t)std::max(1, na) * TC, false));
-    RCHK(q->out_expired.reserve(TC, false));
-    RCHK(q->out_rep.reserve(TC * 8, false));
-    RCHK(q->sc_ochunk.reserve(TC * 8, false));
-    RCHK(q->sc_osend.reserve(TC * 8, false));
-    if (q->given) RCHK(q->out_order.reserve(TC * 8, false));
-    HIPCHK(hipMemsetAsync(q->out_nulls.p, 0, q->out_nulls.cap, s));
-    HIPCHK(hipMemsetAsync(q->out_expired.p, 0, q->out_expired.cap, s));
-    q->zeroed_nulls = q->out_nulls.p;
-    q->zeroed_expired = q->out_expired.p;
-    if (xs) {
-        launch_scx_rows(s, M, n_old, q->sc_pcb.as<int64_t>(), nb, q->sc_skey.as<u64>(), q->scx_fe.as<u32>(),
-                        q->scx_fpre.as<u32>(), q->scx_last.as<u32>(), q->scx_rows.as<u32>(), q->scx_rank.as<int64_t>(),
-                        q->sc_sval.as<u64>(), q->sc_send.as<int64_t>(), q->scx_clk.as<int64_t>(),
-                        q->pend_ts.as<int64_t>(), q->pend_gidx.as<u64>(), q->kt.dev(), q->kp, q->ap, cur_on, 1, T,
-                        q->out_ts.as<int64_t>(), q->out_keys.as<int64_t>(), q->out_vals.as<u64>(),
-                        q->out_nulls.as<unsigned char>(), q->out_expired.as<unsigned char>(), q->out_rep.as<int64_t>(),
-                        q->sc_ochunk.as<int64_t>(), q->sc_osend.as<int64_t>());
-    } else if (xt) {
-        launch_scxt_rows(s, M, n_old, q->sc_pcb.as<int64_t>(), nb, q->sc_skey.as<u64>(), q->scx_fe.as<u32>(),
-                         q->scx_fpre.as<u32>(), q->scx_last.as<u32>(), q->sc_ghead.as<u32>(), q->scx_rows.as<u32>(),
-                         q->sc_slast.as<u32>(), q->sc_sval.as<u64>(), q->sc_chunk.as<int64_t>(),
-                         q->sc_send.as<int64_t>(), q->scx_clk.as<int64_t>(), q->pend_ts.as<int64_t>(),
-                         q->pend_gidx.as<u64>(), q->kt.dev(), q->kp, q->ap, cur_on, T, q->out_ts.as<int64_t>(),
-                         q->out_keys.as<int64_t>(), q->out_vals.as<u64>(), q->out_nulls.as<unsigned char>(),
-                         q->out_expired.as<unsigned char>(), q->out_rep.as<int64_t>(), q->sc_ochunk.as<int64_t>(),
-                         q->sc_osend.as<int64_t>());
-    } else {
-        launch_sc_emit(s, M, n_old, all_heads ? nullptr : q->sc_ghead.as<u32>(), q->sc_pre.as<u32>(), q->sc_slast.as<u32>(),
-                       q->sc_sval.as<u64>(), q->pend_pos.as<u32>(), q->pend_ts.as<int64_t>(), q->pend_gidx.as<u64>(),
-                       q->sc_chunk.as<int64_t>(), q->sc_send.as<int64_t>(), q->kt.dev(), q->kp, na, T,
-                       q->out_ts.as<int64_t>(), q->out_keys.as<int64_t>(), q->out_vals.as<u64>(),
-                       q->out_rep.as<int64_t>(), all_heads ? nullptr : q->sc_ochunk.as<int64_t>(),
-                       q->sc_osend.as<int64_t>(), q->given ? q->out_order.as<int64_t>() : nullptr);
-    }
-    HIPCHK(hipGetLastError());
-    PinnedVec<int64_t>& fo = host_out ? q->out.flush_offsets : q->dev_flush_offsets;
-    PinnedVec<int64_t>& fc = host_out ? q->out.flush_clock : q->dev_flush_clock;
-    fo.assign(1, 0);
-    fc.clear();
-    if (!(xs || xt)) {
-        // a flush ends where the row's chunk changes: flags, their scan, the offsets and clocks
-        RCHK(q->sc_bclk.reserve((size_t)std::max(nb, 1) * 8, false));
-        RCHK(q->sc_h.reserve((size_t)std::max(nb, 1) * 8 + 64));
-        for (int i = 0; i < nb; i++) q->sc_h.as<int64_t>()[i] = bounds[i].clock;
-        if (nb) HIPCHK(hipMemcpyAsync(q->sc_bclk.p, q->sc_h.p, (size_t)nb * 8, hipMemcpyHostToDevice, s));
-        RCHK(q->h_small_sc.reserve(64));
-        int64_t nf = T;  // (every row its own chunk: a flush per row, no flags to scan)
-        if (!all_heads) {
-            RCHK(q->sc_fflag.reserve((size_t)(T + 1) * 4, false));
-            RCHK(q->sc_tmp.reserve((size_t)((T + 1 + kTile - 1) / kTile + 16) * 8, false));
-            launch_sc_flush_flags(s, T, q->sc_ochunk.as<int64_t>(), q->sc_fflag.as<u32>());
-            launch_scan_sum_large_u32(s, q->sc_fflag.as<u32>(), T + 1, q->sc_tmp.as<int64_t>());
-            HIPCHK(hipMemcpyAsync(q->h_small_sc.p, q->sc_fflag.as<uint32_t>() + T, 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            nf = *q->h_small_sc.as<uint32_t>();
-        }
-        q->compact_now = false;
-        const bool want_compact = q->compact_flushes && q->rate.kind == SH_RATE_NONE && !q->xmode && !hv && nf > 0 && nf == T;
-        if (all_heads && want_compact) {
-            // (a flush per row: check the rows' clocks against their timestamps before writing any flush)
-            launch_sc_clock_is_ts(s, T, q->sc_osend.as<int64_t>(), q->sc_slp.as<int64_t>(), cv0 ? 1 : 0, clock0,
-                                  q->out_ts.as<int64_t>(), q->h_small_sc.as<uint32_t>() + 1);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(s));
-            q->compact_now = q->h_small_sc.as<uint32_t>()[1] == 1u;
-        }
-        if (!q->compact_now) {
-            RCHK(q->sc_fo.reserve((size_t)std::max<int64_t>(nf, 1) * 8, false));
-            RCHK(q->sc_fc.reserve((size_t)std::max<int64_t>(nf, 1) * 8, false));
-            launch_sc_flushes(s, T, q->sc_osend.as<int64_t>(), all_heads ? nullptr : q->sc_fflag.as<u32>(),
-                              q->sc_slp.as<int64_t>(), cv0 ? 1 : 0, clock0, q->sc_bclk.as<int64_t>(),
-                              q->sc_fo.as<int64_t>(), q->sc_fc.as<int64_t>());
-            HIPCHK(hipGetLastError());
-        }
-        if (!all_heads && want_compact) {
-            // one row per flush: offsets implicit; clocks implicit too when each equals its row's ts
-            launch_flush_clock_is_ts(s, nf, q->sc_fc.as<int64_t>(), q->out_ts.as<int64_t>(), q->h_small_sc.as<uint32_t>() + 1);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(s));
-            q->compact_now = q->h_small_sc.as<uint32_t>()[1] == 1u;
-        }
-        if (!q->compact_now) {
-            fo.resize((size_t)nf + 1);
-            fc.resize((size_t)nf);
-            if (nf) {
-                HIPCHK(hipMemcpyAsync(fo.data() + 1, q->sc_fo.p, (size_t)nf * 8, hipMemcpyDeviceToHost, s));
-                HIPCHK(hipMemcpyAsync(fc.data(), q->sc_fc.p, (size_t)nf * 8, hipMemcpyDeviceToHost, s));
-            }
-        }
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    // every row's chunk and send
-    const int64_t* och = nullptr;
-    const int64_t* osd = nullptr;
-    if (T && (xs || xt)) {
-        RCHK(q->sc_ho.reserve((size_t)2 * T * 8 + 64));
-        int64_t* hs = q->sc_ho.as<int64_t>();
-        HIPCHK(hipMemcpyAsync(hs, q->sc_ochunk.p, (size_t)T * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(hs + T, q->sc_osend.p, (size_t)T * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        och = hs;  // read in place from the pinned landing area
-        osd = hs + T;
-    }
-    if (xs || xt) {
-        fo.reserve((size_t)T + 1);  // (one pinned allocation, not a doubling series)
-        fc.reserve((size_t)T);
-        for (int64_t i = 0; i < T; i++) {
-            if (i + 1 == T || och[i + 1] != och[i]) {
-                fo.push_back(i + 1);
-                fc.push_back(osd[i] >= 0 ? sl[osd[i]] : bounds[-osd[i] - 1].clock);
-            }
-        }
-    }
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, q->ev_agg0, q->ev_agg1);
-    q->stats.main_kernel_ms += ms;
-    if (host_out) {
-        OutHost& o = q->out;
-        o.ts.resize(T);
-        o.expired.resize(T);
-        o.rep.resize(T);
-        o.keys.resize((size_t)nk * T);
-        o.vals.resize((size_t)na * T);
-        o.nulls.resize((size_t)na * T);
-        if (T) {
-            HIPCHK(hipMemcpyAsync(o.expired.data(), q->out_expired.p, T, hipMemcpyDeviceToHost, s));
-            if (na) HIPCHK(hipMemcpyAsync(o.nulls.data(), q->out_nulls.p, (size_t)na * T, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(o.ts.data(), q->out_ts.p, T * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(o.rep.data(), q->out_rep.p, T * 8, hipMemcpyDeviceToHost, s));
-            if (nk) HIPCHK(hipMemcpyAsync(o.keys.data(), q->out_keys.p, (size_t)nk * T * 8, hipMemcpyDeviceToHost, s));
-            if (na) HIPCHK(hipMemcpyAsync(o.vals.data(), q->out_vals.p, (size_t)na * T * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-        }
-        // sharded owner: a row's merge order is the global stream index of its group's first event in the chunk
-        if (q->given) {
-            q->order_host.resize(T);
-            if (T) HIPCHK(hipMemcpyAsync(q->order_host.data(), q->out_order.p, T * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-        }
-    } else {
-        q->dev_out.n_rows = T;
-    }
-    return SH_OK;
-}
-
-// timeBatch(T, true) with expired output: the open window closed by a TIMER without events
-// (sh_advance_time): one flush of its keys' EXPIRED rows (empty state) at clock `now`
-static int sc_expire_pending(sh_query* q, int64_t now, bool host_out) {
-    hipStream_t s = q->ctx->stream;
-    const int64_t M = q->n_pend;
-    const int nk = q->kp.n, na = q->ap.n;
-    RCHK(q->sc_skey.reserve((size_t)M * 8, false));
-    RCHK(q->sc_skey2.reserve((size_t)M * 8, false));
-    RCHK(q->sc_idx.reserve((size_t)M * 4, false));
-    RCHK(q->sc_idx2.reserve((size_t)M * 4, false));
-    RCHK(q->sc_chunk.reserve((size_t)M * 8, false));
-    RCHK(q->sc_send.reserve((size_t)M * 8, false));
-    RCHK(q->sc_hd.reserve((size_t)(M + 1) * 4, false));
-    RCHK(q->sc_pos.reserve((size_t)(M + 1) * 4, false));
-    RCHK(q->sc_starts.reserve((size_t)(M + 1) * 4, false));
-    RCHK(q->sc_tmp.reserve((size_t)((M + 1 + kTile - 1) / kTile + 16) * 8, false));
-    RCHK(q->scx_fe.reserve((size_t)(M + 1) * 4, false));
-    RCHK(q->scx_fpre.reserve((size_t)(M + 1) * 4, false));
-    RCHK(q->scx_last.reserve((size_t)M * 4, false));
-    RCHK(q->sc_pcb.reserve(8, false));
-    launch_sc_keys(s, M, M, q->sc_pcb.as<int64_t>(), 0, q->pend_pos.as<u32>(), q->pend_gidx.as<u64>(), 0, 0, 0,
-                   q->sc_skey.as<u64>(), q->sc_idx.as<u32>(), q->sc_chunk.as<int64_t>(), q->sc_send.as<int64_t>());
-    size_t tb = 0;
-    if (sort_u64_pairs(nullptr, &tb, nullptr, nullptr, nullptr, nullptr, M, s))
-        return sh_fail(SH_ERR_DEVICE, "stream.current: sort sizing");
-    RCHK(q->sc_sort.reserve(std::max<size_t>(tb, 16), false));
-    if (sort_u64_pairs(q->sc_sort.p, &tb, q->sc_skey.as<u64>(), q->sc_skey2.as<u64>(), q->sc_idx.as<u32>(),
-                       q->sc_idx2.as<u32>(), M, s))
-        return sh_fail(SH_ERR_DEVICE, "stream.current: sort failed");
-    launch_rate_segments(s, M, q->sc_skey2.as<u64>(), q->sc_idx2.as<u32>(), 1, 0, q->sc_hd.as<u32>(),
-                         q->sc_pos.as<u32>(), q->sc_starts.as<u32>(), q->sc_tmp.as<int64_t>());
-    HIPCHK(hipMemsetAsync(q->scx_fe.p, 0, (size_t)(M + 1) * 4, s));
-    launch_scx_first(s, M, q->sc_hd.as<u32>(), q->sc_pos.as<u32>(), q->sc_starts.as<u32>(), q->sc_idx2.as<u32>(),
-                     q->scx_fe.as<u32>(), q->scx_fpre.as<u32>(), q->scx_last.as<u32>());
-    HIPCHK(hipMemcpyAsync(q->scx_fpre.p, q->scx_fe.p, (size_t)(M + 1) * 4, hipMemcpyDeviceToDevice, s));
-    launch_scan_sum_large_u32(s, q->scx_fpre.as<u32>(), M + 1, q->sc_tmp.as<int64_t>());
-    RCHK(q->h_small_sc.reserve(64));
-    HIPCHK(hipMemcpyAsync(q->h_small_sc.p, q->scx_fpre.as<uint32_t>() + M, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    const int64_t T = *q->h_small_sc.as<uint32_t>();
-    const int64_t TC = std::max<int64_t>(T, 1);
-    RCHK(q->out_ts.reserve(TC * 8, false));
-    RCHK(q->out_keys.reserve((size_t)std::max(1, nk) * TC * 8, false));
-    RCHK(q->out_vals.reserve((size_t)std::max(1, na) * TC * 8, false));
-    RCHK(q->out_nulls.reserve((size_t)std::max(1, na) * TC, false));
-    RCHK(q->out_expired.reserve(TC, false));
-    RCHK(q->out_rep.reserve(TC * 8, false));
-    q->zeroed_nulls = nullptr;
-    q->zeroed_expired = nullptr;
-    launch_scx_pending_rows(s, M, q->scx_fe.as<u32>(), q->scx_fpre.as<u32>(), q->scx_last.as<u32>(),
-                            q->pend_pos.as<u32>(), q->pend_gidx.as<u64>(), q->kt.dev(), q->kp, q->ap, now, T,
-                            q->out_ts.as<int64_t>(), q->out_keys.as<int64_t>(), q->out_vals.as<u64>(),
-                            q->out_nulls.as<unsigned char>(), q->out_expired.as<unsigned char>(),
-                            q->out_rep.as<int64_t>());
-    HIPCHK(hipGetLastError());
-    PinnedVec<int64_t>& fo = host_out ? q->out.flush_offsets : q->dev_flush_offsets;
-    PinnedVec<int64_t>& fc = host_out ? q->out.flush_clock : q->dev_flush_clock;
-    fo.assign(1, 0);
-    fc.clear();
-    if (T) {
-        fo.push_back(T);
-        fc.push_back(now);
-    }
-    if (host_out) {
-        OutHost& o = q->out;
-        o.ts.resize(T);
-        o.expired.resize(T);
-        o.rep.resize(T);
-        o.keys.resize((size_t)nk * T);
-        o.vals.resize((size_t)na * T);
-        o.nulls.resize((size_t)na * T);
-        if (T) {
-            HIPCHK(hipMemcpyAsync(o.expired.data(), q->out_expired.p, T, hipMemcpyDeviceToHost, s));
-            if (na) HIPCHK(hipMemcpyAsync(o.nulls.data(), q->out_nulls.p, (size_t)na * T, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(o.ts.data(), q->out_ts.p, T * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(o.rep.data(), q->out_rep.p, T * 8, hipMemcpyDeviceToHost, s));
-            if (nk) HIPCHK(hipMemcpyAsync(o.keys.data(), q->out_keys.p, (size_t)nk * T * 8, hipMemcpyDeviceToHost, s));
-            if (na) HIPCHK(hipMemcpyAsync(o.vals.data(), q->out_vals.p, (size_t)na * T * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-        }
-    } else {
-        q->dev_out.n_rows = T;
-    }
-    return SH_OK;
-}
-
 // entries [lo, lo + n) of the pending buffer moved to its front: one copy per column when the ranges
 // do not overlap, else through the query's staging buffer (r05: a buffer allocated per push cost a
 // hipMalloc, a stream drain and a hipFree on every stream.current push)
@@ -1397,25 +910,43 @@ bool query_small_eligible(const sh_query* q, int64_t N) {
     return w == SH_WIN_LENGTH_BATCH || (w == SH_WIN_TIME_BATCH && q->e0_valid && q->clock_valid);
 }
 
+// the small-push report in coherent pinned memory names token `t` or a later one
+static bool small_reported(const sh_query* q, uint64_t t) { return *(volatile uint64_t*)&q->small_res->token >= t; }
+
+// Spin until the small-push kernel given token `t` has reported. Tokens come from ++q->small_token and
+// reports arrive in launch order, so the reported token only grows: `token >= t` says that kernel or a
+// later one has reported, and for the newest token it is the same test as `token == t`. Every 1024
+// polls the stream is asked whether it still runs; on an idle stream without the report the wait ends
+// with *reported = false, which the caller judges.
+static int wait_small_report(sh_query* q, uint64_t t, bool* reported) {
+    for (int spin = 0; !(*reported = small_reported(q, t)); spin++) {
+        if ((spin & 1023) != 1023) continue;
+        const hipError_t e = hipStreamQuery(q->ctx->stream);
+        if (e == hipSuccess) {
+            *reported = small_reported(q, t);
+            break;
+        }
+        if (e != hipErrorNotReady) return sh_fail(SH_ERR_DEVICE, std::string("small push: ") + hipGetErrorString(e));
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return SH_OK;
+}
+
+// ... for a caller that reads the report: an idle stream without it is an error
+static int need_small_report(sh_query* q, uint64_t t) {
+    bool reported = false;
+    RCHK(wait_small_report(q, t, &reported));
+    return reported ? SH_OK : sh_fail(SH_ERR_DEVICE, "small push: no report");
+}
+
 // The last asynchronous small push's report: verified once its token has arrived (wait: spin for
 // it). Reports arrive in launch order and the key table's overflow flag is sticky, so any later
 // report covers the earlier pushes too.
 static int small_verify(sh_query* q, bool wait) {
     if (!q->async_tok) return SH_OK;
+    if (!wait && !small_reported(q, q->async_tok)) return SH_OK;
+    RCHK(need_small_report(q, q->async_tok));
     volatile SmallRes* r = q->small_res;
-    hipStream_t s = q->ctx->stream;
-    for (int spin = 0; *(volatile uint64_t*)&r->token < q->async_tok; spin++) {
-        if (!wait) return SH_OK;
-        if ((spin & 1023) == 1023) {
-            const hipError_t e = hipStreamQuery(s);
-            if (e == hipSuccess) {
-                if (*(volatile uint64_t*)&r->token < q->async_tok) return sh_fail(SH_ERR_DEVICE, "small push: no report");
-                break;
-            }
-            if (e != hipErrorNotReady) return sh_fail(SH_ERR_DEVICE, std::string("small push: ") + hipGetErrorString(e));
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
     uint32_t ctrl[4];
     for (int i = 0; i < 4; i++) ctrl[i] = r->ctrl[i];
     q->async_tok = 0;
@@ -1457,17 +988,11 @@ static int small_async(sh_query* q, bool* done) {
         }
         q->zc_slot = sl;
     }
-    volatile SmallRes* r = q->small_res;
     hipStream_t s = q->ctx->stream;
     const int slot = q->zc_next;
-    // the slot's previous reader has finished (reports arrive in launch order)
-    for (int spin = 0; *(volatile uint64_t*)&r->token < q->zc_tok[slot]; spin++) {
-        if ((spin & 1023) == 1023) {
-            const hipError_t e = hipStreamQuery(s);
-            if (e == hipSuccess) break;
-            if (e != hipErrorNotReady) return sh_fail(SH_ERR_DEVICE, std::string("small push: ") + hipGetErrorString(e));
-        }
-    }
+    // the slot's previous reader has finished: it has reported, or the stream is idle (nothing reads the slot)
+    bool reported = false;
+    RCHK(wait_small_report(q, q->zc_tok[slot], &reported));
     char* hbase = q->zc_ring + (size_t)slot * q->zc_slot;
     char* dbase = q->zc_ring_dev + (size_t)slot * q->zc_slot;
     sh_batch dv = *hb;
@@ -1487,21 +1012,8 @@ static int small_async(sh_query* q, bool* done) {
         }
         off += a16((size_t)kSmallMax * ts_);
     }
-    WinParams wp{};
-    wp.kind = q->d.window;
-    wp.e0_valid = q->e0_valid;
-    wp.clock_valid = q->clock_valid;
-    wp.L = wp.T = q->d.window_param;
-    wp.cal = q->cal;
-    wp.cal_tz = q->cal_tz;
-    wp.E0 = q->E0;
-    wp.clock0 = q->clock;
-    wp.W_open = q->W_open;
-    wp.n_pend = q->n_pend;
-    wp.send_size = hb->send_size;
-    wp.N = N;
     const uint64_t token = ++q->small_token;
-    launch_small_push(s, dv.ts, cs, q->fp, wp, q->kp, q->kt.dev(), q->ap, q->pend_pos.as<u32>(), q->pend_ts.as<int64_t>(),
+    launch_small_push(s, dv.ts, cs, q->fp, base_win_params(q, hb->send_size, N), q->kp, q->kt.dev(), q->ap, q->pend_pos.as<u32>(), q->pend_ts.as<int64_t>(),
                       q->pend_vals.as<u64>(), q->pend_cap, q->pend_gidx.as<u64>(), q->seq, q->small_res_dev, token,
                       true);
     HIPCHK(hipGetLastError());
@@ -1583,13 +1095,10 @@ static int xt_probe(sh_query* q, const sh_batch* b, int64_t L, int64_t* f, int64
     if (j == ~0ull) return sh_fail(SH_ERR_INVALID, "externalTimeBatch timeout: no send reaches the scheduled time");
     *f = ss > 0 ? (int64_t)j * ss : 0;
     const int64_t last = ss > 0 ? std::min<int64_t>(((int64_t)j + 1) * ss, N) - 1 : N - 1;
-    ColSet cs{};
-    cs.n = q->d.n_cols;
-    for (int c = 0; c < q->d.n_cols; c++) { cs.type[c] = q->load_type[c]; cs.ptr[c] = b->cols[c]; }
     const int64_t lo_m = INT64_MIN;
     HIPCHK(hipMemsetAsync(d + 1, 0, 8, s));
     HIPCHK(hipMemcpyAsync(d + 2, &lo_m, 8, hipMemcpyHostToDevice, s));
-    launch_xt_count_pass(s, cs, q->fp, *f, d + 1, q->d.ts_col, (long long*)(d + 2));
+    launch_xt_count_pass(s, col_set(q, b), q->fp, *f, d + 1, q->d.ts_col, (long long*)(d + 2));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h + 1, d + 1, 16, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(h, b->ts + last, 8, hipMemcpyDeviceToHost, s));
@@ -1698,7 +1207,6 @@ static int try_small_push(sh_query* q, const sh_batch* b, bool* done) {
     *done = false;
     const int64_t N = b->n;
     if (!query_small_eligible(q, N)) return SH_OK;
-    const int w = q->d.window;
     if (!q->small_res) {
         if (hipHostMalloc((void**)&q->small_res, sizeof(SmallRes), hipHostMallocCoherent | hipHostMallocMapped) !=
                 hipSuccess ||
@@ -1712,40 +1220,14 @@ static int try_small_push(sh_query* q, const sh_batch* b, bool* done) {
         if (*done) return SH_OK;
     }
     SH_TMARK(1);
-    hipStream_t s = q->ctx->stream;
-    ColSet cs{};
-    cs.n = q->d.n_cols;
-    for (int c = 0; c < q->d.n_cols; c++) { cs.type[c] = q->load_type[c]; cs.ptr[c] = b->cols[c]; }
-    WinParams wp{};
-    wp.kind = w;
-    wp.e0_valid = q->e0_valid;
-    wp.clock_valid = q->clock_valid;
-    wp.L = wp.T = q->d.window_param;
-    wp.cal = q->cal;
-    wp.cal_tz = q->cal_tz;
-    wp.E0 = q->E0;
-    wp.clock0 = q->clock;
-    wp.W_open = q->W_open;
-    wp.n_pend = q->n_pend;
-    wp.send_size = b->send_size;
-    wp.N = N;
     const uint64_t token = ++q->small_token;
-    launch_small_push(s, b->ts, cs, q->fp, wp, q->kp, q->kt.dev(), q->ap, q->pend_pos.as<u32>(), q->pend_ts.as<int64_t>(),
-                      q->pend_vals.as<u64>(), q->pend_cap, q->pend_gidx.as<u64>(), q->seq, q->small_res_dev, token);
+    launch_small_push(q->ctx->stream, b->ts, col_set(q, b), q->fp, base_win_params(q, b->send_size, N), q->kp, q->kt.dev(),
+                      q->ap, q->pend_pos.as<u32>(), q->pend_ts.as<int64_t>(), q->pend_vals.as<u64>(), q->pend_cap,
+                      q->pend_gidx.as<u64>(), q->seq, q->small_res_dev, token);
     HIPCHK(hipGetLastError());
     SH_TMARK(2);
+    RCHK(need_small_report(q, token));  // (the newest token: nothing later can have reported in its place)
     volatile SmallRes* r = q->small_res;
-    for (int spin = 0; *(volatile uint64_t*)&r->token != token; spin++) {
-        if ((spin & 1023) == 1023) {  // every ~1000 polls: is the stream still running?
-            const hipError_t e = hipStreamQuery(s);
-            if (e == hipSuccess) {
-                if (*(volatile uint64_t*)&r->token != token) return sh_fail(SH_ERR_DEVICE, "small push: no report");
-                break;
-            }
-            if (e != hipErrorNotReady) return sh_fail(SH_ERR_DEVICE, std::string("small push: ") + hipGetErrorString(e));
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
     SH_TMARK(3);
     uint32_t ctrl[4];
     for (int i = 0; i < 4; i++) ctrl[i] = r->ctrl[i];
@@ -1770,15 +1252,10 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
     q->x_stamps.clear();
     hipStream_t s = q->ctx->stream;
     q->out.reset();
-    q->dev_flush_offsets.assign(1, 0);
-    q->dev_flush_clock.clear();
-    q->flush_window.clear();
-    q->dev_out = sh_out{};
+    reset_call_output(q);
     q->stats = sh_stats{};
     q->agg_bytes = 0;
     q->order_host.clear();
-    q->ms_ready = false;
-    q->tail.active = false;
     int64_t N = b->n;
     const bool cv0 = q->clock_valid;
     const int64_t clock0 = q->clock, seq0 = q->seq;
@@ -1794,10 +1271,7 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
     {
         bool done = false;
         RCHK(try_small_push(q, b, &done));
-        if (done) {
-            finish_out(q, host_out, out);
-            return SH_OK;
-        }
+        if (done) return finish_out(q, host_out, out);
         RCHK(small_verify(q, true));  // the full pipeline reads the state the queued appends left
     }
     sh_batch zc_dev;
@@ -1810,29 +1284,14 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
     HIPCHK(hipEventRecord(q->ev_push0, s));
     if (N > 0 && q->partitioned && !q->p0_known) RCHK(resolve_first_partition(q, b));
     if (N > 0 && !(q->partitioned && !q->p0_known)) {
-        ColSet cs{};
-        cs.n = q->d.n_cols;
-        for (int c = 0; c < q->d.n_cols; c++) { cs.type[c] = q->load_type[c]; cs.ptr[c] = b->cols[c]; }
+        const ColSet cs = col_set(q, b);
         int nblk = (int)((N + kTile - 1) / kTile);
         RCHK(q->blk_pass.reserve(nblk * 8, false));
         RCHK(q->blk_tl.reserve(nblk * 8, false));
         RCHK(q->blk_first.reserve(scan_blocks_first_bytes(nblk), false));
-        WinParams wp{};
-        wp.kind = q->d.window;
-        wp.e0_valid = q->e0_valid;
-        wp.clock_valid = q->clock_valid;
+        WinParams wp = base_win_params(q, b->send_size, N);
         wp.has_start = q->d.has_start_time;
-        wp.L = q->d.window_param;
-        wp.T = q->d.window_param;
-        wp.cal = q->cal;
-        wp.cal_tz = q->cal_tz;
-        wp.E0 = q->E0;
         wp.start_time = q->d.start_time;
-        wp.clock0 = q->clock;
-        wp.W_open = q->W_open;
-        wp.n_pend = q->n_pend;
-        wp.send_size = b->send_size;
-        wp.N = N;
         wp.ts_col = q->d.ts_col;
         wp.start_col = q->d.start_col;
         wp.xm0 = q->xm;
@@ -2025,12 +1484,7 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
             // every passing event is emitted now: all of them join the pending entries, the rows come
             // from the open window's earlier events + these; the last window's entries stay queued
             const int64_t n_old = q->n_pend, M = n_old + info.total_pass;
-            RCHK(grow_pending(q, M, n_old));
-            launch_compact_pending(s, b->ts, cs, pos_src(q, b), q->ap, 0, N, 0, n_old,
-                                   q->blk_pass.as<int64_t>(), q->pend_pos.as<u32>(), q->pend_ts.as<int64_t>(),
-                                   q->pend_vals.as<u64>(), q->pend_cap, q->given ? q->given_gidx : nullptr,
-                                   q->pend_gidx.as<u64>(), q->seq);
-            HIPCHK(hipGetLastError());
+            RCHK(append_pending(q, b, n_old, M));
             // (a window may close with no passing event in the push: its expired rows still go out)
             if (M > n_old || (q->d.expired_on && !bounds.empty() && n_old > 0))
                 RCHK(sc_rows(q, b, bounds, n_old, M, cv0, clock0, seq0, host_out));
@@ -2063,7 +1517,7 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
     q->stats.events = N;
     q->stats.main_kernel_bytes = q->agg_bytes;
     if (q->xmode) return xout_finish(q, host_out_req, out);
-    finish_out(q, host_out, out);
+    RCHK(finish_out(q, host_out, out));
     SH_TMARK(6);
     return SH_OK;
 }
@@ -2219,18 +1673,8 @@ static int push_any_core(sh_query* q, const sh_batch* dev, bool host_out, const 
 int query_peek(sh_query* q, int64_t* n_rows) {
     *n_rows = 0;
     if (q->n_pend == 0) return SH_OK;
-    hipStream_t s = q->ctx->stream;
-    q->dev_flush_offsets.assign(1, 0);
-    q->dev_flush_clock.clear();
-    q->flush_window.clear();
-    q->dev_out = sh_out{};
-    q->ms_ready = false;
-    q->tail.active = false;
-    std::vector<Segment> segs{Segment{0, q->n_pend}};
-    std::vector<int64_t> clocks{q->clock}, windows{q->W_open};
-    RCHK(run_closed(q, segs, clocks, windows, nullptr, false));
-    HIPCHK(hipStreamSynchronize(s));
-    RCHK(closed_finish(q, false));
+    reset_call_output(q);
+    RCHK(close_open_window(q, q->clock, false));
     *n_rows = q->dev_out.n_rows;
     q->dev_flush_offsets.assign(1, 0);
     q->dev_flush_clock.clear();
@@ -2328,17 +1772,11 @@ static int advance_core(sh_query* q, int64_t now, bool host_out_req, const sh_ou
     q->x_closes.clear();
     q->out.reset();
     q->order_host.clear();
-    q->dev_flush_offsets.assign(1, 0);
-    q->dev_flush_clock.clear();
-    q->flush_window.clear();
-    q->dev_out = sh_out{};
-    q->ms_ready = false;
-    q->tail.active = false;
+    reset_call_output(q);
     // TimestampGeneratorImpl.setCurrentTimestamp only moves the clock forward (:104-122)
     if (q->clock_valid && now < q->clock) {
         if (q->xmode) return xout_finish(q, host_out_req, out);
-        finish_out(q, host_out, out);
-        return SH_OK;
+        return finish_out(q, host_out, out);
     }
     q->clock = now;
     q->clock_valid = true;
@@ -2346,11 +1784,7 @@ static int advance_core(sh_query* q, int64_t now, bool host_out_req, const sh_ou
         // an externalTimeBatch timeout: the open batch, if it holds events not yet sent (:256-275)
         if (q->xt_nnew > 0 && q->n_pend > 0) {
             if (q->xmode) q->x_stamps.assign(1, q->xm);  // (lastCurrentEventTime: the expired rows' stamp)
-            std::vector<Segment> segs{Segment{0, q->n_pend}};
-            std::vector<int64_t> clocks{now}, windows{q->W_open};
-            RCHK(run_closed(q, segs, clocks, windows, nullptr, host_out));
-            HIPCHK(hipStreamSynchronize(q->ctx->stream));
-            RCHK(closed_finish(q, host_out));
+            RCHK(close_open_window(q, now, host_out));
         }
         q->xt_nnew = 0;
         q->xt_L = now + q->xt_timeout;
@@ -2364,18 +1798,13 @@ static int advance_core(sh_query* q, int64_t now, bool host_out_req, const sh_ou
             if (q->d.expired_on) RCHK(sc_expire_pending(q, now, host_out));
             q->n_pend = 0;
         } else if (W > q->W_open && q->n_pend > 0) {
-            std::vector<Segment> segs{Segment{0, q->n_pend}};
-            std::vector<int64_t> clocks{now}, windows{q->W_open};
-            RCHK(run_closed(q, segs, clocks, windows, nullptr, host_out));
+            RCHK(close_open_window(q, now, host_out));
             q->n_pend = 0;
-            HIPCHK(hipStreamSynchronize(q->ctx->stream));
-            RCHK(closed_finish(q, host_out));
         }
         q->W_open = std::max(q->W_open, W);
     }
     if (q->xmode) return xout_finish(q, host_out_req, out);
-    finish_out(q, host_out, out);
-    return SH_OK;
+    return finish_out(q, host_out, out);
 }
 
 static int advance_any(sh_query* q, int64_t now, const sh_out** out);
@@ -2461,9 +1890,7 @@ int reserve_ms_counts(sh_query* q, const TileMap& m) {
 int run_multisplit(sh_query* q, int64_t hi, const sh_batch* b, bool counted, bool wide) {
     hipStream_t s = q->ctx->stream;
     int P = q->P;
-    ColSet cs{};
-    cs.n = q->d.n_cols;
-    for (int c = 0; c < q->d.n_cols; c++) { cs.type[c] = q->load_type[c]; cs.ptr[c] = b ? b->cols[c] : nullptr; }
+    const ColSet cs = col_set(q, b);
     const TileMap m = counted ? make_tile_map(q->n_pend, hi) : make_tile_map(0, hi);
     RCHK(reserve_ms_counts(q, m));  // (the size k_boundaries' counts were written into: no regrowth)
     RCHK(q->part_off.reserve((P + 1) * 8, false));
@@ -2533,28 +1960,17 @@ int query_close_given(sh_query* q, bool host_out_req, const sh_out** out) {
     if (q->xmode) given_closes(q);
     q->out.reset();
     q->order_host.clear();
-    q->dev_flush_offsets.assign(1, 0);
-    q->dev_flush_clock.clear();
-    q->flush_window.clear();
-    q->dev_out = sh_out{};
+    reset_call_output(q);
     q->stats = sh_stats{};
-    q->ms_ready = false;
-    q->tail.active = false;
     if (q->given_W_end > q->W_open) {
-        if (q->n_pend > 0 && q->d.stream_current) {
-            q->n_pend = 0;  // (RESET: the events went out as they arrived; current output only)
-        } else if (q->n_pend > 0) {
-            std::vector<Segment> segs{Segment{0, q->n_pend}};
-            std::vector<int64_t> clocks{given_flush_clock(q, q->W_open)}, windows{q->W_open};
-            RCHK(run_closed(q, segs, clocks, windows, nullptr, host_out));
-            q->n_pend = 0;
-            HIPCHK(hipStreamSynchronize(q->ctx->stream));
-            RCHK(closed_finish(q, host_out));
-        }
+        if (q->n_pend > 0 && !q->d.stream_current)
+            RCHK(close_open_window(q, given_flush_clock(q, q->W_open), host_out));
+        // (stream.current.event, RESET: the events went out as they arrived; current output only)
+        q->n_pend = 0;
         q->W_open = q->given_W_end;
     }
     if (q->xmode) return xout_finish(q, host_out_req, out);
-    finish_out(q, host_out, out);
+    RCHK(finish_out(q, host_out, out));
     if (q->wide) {
         RCHK(wide_finish(q, host_out_req, out));
         return given_order_host(q, host_out_req, *out);

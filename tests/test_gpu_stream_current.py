@@ -130,6 +130,32 @@ def test_compact_flushes(rt, window, param):
     o.close()
 
 
+@pytest.mark.parametrize("window,param", [("lengthBatch", 50), ("timeBatch", 700)])
+def test_stream_current_all_events_device_output(rt, window, param):
+    """sh_push_device of stream.current.event windows with `all events` output: the CURRENT and EXPIRED rows
+    (their expired and null flags included) read back from device memory equal the oracle's, push by push."""
+    import torch
+    from oracle.oracle import OracleQuery
+    from tests.parity import assert_same
+    ts, cols = stream(12_000, 40, 13)
+    spec = abi.QuerySpec(SCHEMA, window, param, group_by=["k"], aggs=AGGS, stream_current=True, output="all",
+                         key_capacity=64)
+    g, o = rt.GpuQuery(spec), OracleQuery(spec)
+    dev = torch.device("cuda", 0)
+    expired = 0
+    for a, b in ((0, 777), (777, 5_000), (5_000, 12_000)):
+        t = torch.from_numpy(ts[a:b]).to(dev)
+        dc = [torch.from_numpy(np.ascontiguousarray(c[a:b])).to(dev) for c in cols]
+        torch.cuda.synchronize()
+        got = rt.device_out_arrays(g.push_device(len(t), t.data_ptr(), [c.data_ptr() for c in dc], 3))
+        ref = abi.out_arrays(o.push_raw(abi.HostBatch(SCHEMA, ts[a:b], [c[a:b] for c in cols], 3)))
+        assert_same(got, ref, label=f"{window}({param}, true) all events, device output, push at {a}")
+        expired += int(got["expired"].sum())
+    assert expired > 0
+    g.close()
+    o.close()
+
+
 @pytest.mark.parametrize("window", ["time", "externalTime"])
 def test_sliding_device_output_flush_layout(rt, window):
     """sh_push_device of a sliding window: the flush layout is host memory (the ABI contract) — read here
