@@ -279,16 +279,23 @@ int sh_rate_apply_merged(sh_query* q, const sh_out* merged, const sh_out** out);
  * once on a key's final row.
  * The program is a postfix sh_filter_op array like the filter: SH_OP_KEY, SH_OP_AGG, SH_OP_CONST, the six
  * comparisons (Compare executors' promotion as for the filter; a null operand would make a comparison false,
- * CompareConditionExpressionExecutor.java:38-42 — batch-window aggregates are never null) and AND / OR / NOT;
+ * CompareConditionExpressionExecutor.java:38-42 — only an EXPIRED row's aggregates can be null) and AND / OR / NOT;
  * at most 32 ops, boolean result. It is copied. Set once, before the first push (SH_ERR_STATE later or twice);
  * n_ops == 0 is SH_ERR_INVALID.
  * SH_ERR_INVALID: stack underflow or values left on the stack, a key / aggregate number out of range, a result
  * that is not boolean, a boolean fed to a comparison, a relational comparison on a string-id or bool operand,
  * more than 32 ops. SH_ERR_UNSUPPORTED, the message naming the shape (the query then stays on the CPU): window
- * NONE / TIME / EXT_TIME (sliding windows), expired or all-events output, a partitioned query, a group-by
- * the library interns (wide keys), no aggregator, an SH_OP_COL operand (a stream attribute of the
- * representative event). Supported: lengthBatch, timeBatch and externalTimeBatch, plain or with
- * stream.current.event, grouped or not, current-events output. On a live query a having program and
+ * NONE / TIME / EXT_TIME (sliding windows), expired or all-events output on a window other than
+ * lengthBatch(L, true) / timeBatch(T, true) ("having with expired / all-events output on this window: it runs
+ * on lengthBatch(L, true) and timeBatch(T, true) (stream.current.event); the other batch windows run it with
+ * current-events output only"), a partitioned query, a group-by the library interns (wide keys), no aggregator,
+ * an SH_OP_COL operand (a stream attribute of the representative event). Supported: lengthBatch, timeBatch and
+ * externalTimeBatch, plain or with stream.current.event, grouped or not, current-events output; and the two
+ * stream.current.event forms with expired / all-events output as well. There the selector removes a closing
+ * window's events one by one and tests the condition after every removal (QuerySelector.java:280-291,
+ * :325-339): a key's EXPIRED row is that of its last passing removal (count after it, sums / avg null at
+ * count 0, min / max the tracking deque's front or null), at the position of its first passing removal, and
+ * in one chunk a key's CURRENT and EXPIRED rows share one slot (LinkedHashMap.put). On a live query a having program and
  * sh_query_set_ext_timeout, or sh_query_set_ext_replace_ts, refuse each other in either order
  * (SH_ERR_UNSUPPORTED). A having query always gets the full host flush arrays (as a rate-limited query does):
  * sh_query_set_compact_flushes / sh_query_set_device_flushes are ignored for it; the row arrays of

@@ -226,7 +226,8 @@ class QuerySpec:
     start_attr: Optional[str] = None   # externalTimeBatch start time from this attribute
     timeout: Optional[int] = None      # externalTimeBatch(ts, T, start, timeout): scheduler timeout (ms)
     replace_ts: bool = False           # externalTimeBatch(..., timeout, true): replaceTimestampWithBatchEndTime
-    having: object = None              # `having` condition (compile_having syntax); batch windows, current output
+    having: object = None              # `having` condition (compile_having syntax); batch windows with current
+                                       # output, lengthBatch(L, true) / timeBatch(T, true) with any output
     _keep: list = field(default_factory=list, repr=False)
 
     def desc(self) -> QueryDesc:

@@ -599,4 +599,70 @@ __device__ __forceinline__ u64 agg_out_kind(int k, u32 c, u64 fv) {
 }
 __device__ __forceinline__ u64 agg_out(const AggPlan& ap, int a, u32 c, u64 fv) { return agg_out_kind(ap.kind[a], c, fv); }
 
+// stream.current.event batch windows: the first pending entry of window w of a push (0: the window open
+// before it; pcb[w - 1]: the new entry that starts window w), shared by k_scx_* and k_hvx_*
+__device__ __forceinline__ i64 sc_wstart(i64 w, i64 n_old, const i64* pcb) { return w == 0 ? 0 : n_old + pcb[w - 1]; }
+
+// ---- the remove forms of the same fields (AttributeAggregatorExecutor.processRemove), for a batch
+// window's ordered remove pass (sh_having_kernels.hip k_hvx_walk) ----------------------------------------
+// Sum / avg field `cur` after removing x: double / float sums `sum -= v`
+// (SumAttributeAggregatorExecutor.java:164-254), avg `value -= v` (AvgAttributeAggregatorExecutor
+// :143-378, an integer input widened first), long / int sums `sum = (long) ((double) sum - (double) v)`
+// (SumAttributeAggregatorExecutor.java:283-291). The count is the caller's.
+__device__ __forceinline__ u64 unfold_sum(int op, u64 cur, i64 x) {
+    if (op == FOP_ADD_I) return (u64)java_d2l((double)(i64)cur - (double)x);
+    const double xd = op == FOP_ADD_DI ? (double)x : __longlong_as_double(x);
+    return (u64)__double_as_longlong(__longlong_as_double((i64)cur) - xd);
+}
+
+// Min / max with expired output track future states in a deque (MinAttributeAggregatorExecutor.java:86-483,
+// MaxAttributeAggregatorExecutor.java:85-475): processAdd pops the values strictly worse than the new one
+// off the back and appends it, processRemove is removeFirstOccurrence(value) and the value becomes the
+// deque's front, or null when the deque is empty.
+__device__ __forceinline__ bool fop_is_minmax(int op) { return op >= FOP_MIN_I; }
+// `cur > v` (min) / `cur < v` (max) on the unboxed values of the field's type; false on NaN
+__device__ __forceinline__ bool fop_worse(int op, u64 cur, u64 v) {
+    const bool is_min = op == FOP_MIN_I || op == FOP_MIN_D || op == FOP_MIN_F;
+    if (op <= FOP_MAX_I) return is_min ? (i64)cur > (i64)v : (i64)cur < (i64)v;
+    const double a = __longlong_as_double((i64)cur), b = __longlong_as_double((i64)v);
+    if (op <= FOP_MAX_D) return is_min ? a > b : a < b;
+    return is_min ? (float)a > (float)b : (float)a < (float)b;
+}
+// boxed equality: Long.equals / Integer.equals by value, Double.equals / Float.equals by bits with every
+// NaN equal (doubleToLongBits / floatToIntBits)
+__device__ __forceinline__ bool fop_equal(int op, u64 a, u64 b) {
+    if (op <= FOP_MAX_I) return a == b;
+    const double x = __longlong_as_double((i64)a), y = __longlong_as_double((i64)b);
+    if (op <= FOP_MAX_D) return (x != x && y != y) || a == b;
+    const float fx = (float)x, fy = (float)y;
+    return (fx != fx && fy != fy) || __float_as_uint(fx) == __float_as_uint(fy);
+}
+// The deque holds entry numbers: d[h, h + len) of the run's own slots; `vals` is the field's value
+// column of the pending entries.
+// processAdd of entry e (value x); nothing is ever removed from the front while a run is added, so h
+// stays where the run's slots begin
+__device__ __forceinline__ void fop_dq_add(int op, u32* d, u32& len, const u64* __restrict__ vals, u32 e, u64 x) {
+    u32 n = len;
+    while (n > 0 && fop_worse(op, vals[d[n - 1]], x)) n--;
+    d[n] = e;
+    len = n + 1;
+}
+// processRemove of value x: the first element equal to x leaves — at the front in the common case (the
+// removals come in arrival order); past it, the elements before it move up one slot. Returns whether the
+// deque still holds a value and then leaves it in *front.
+__device__ __forceinline__ bool fop_dq_remove(int op, u32* d, u32& h, u32& len, const u64* __restrict__ vals, u64 x,
+                                             u64* front) {
+    u32 found = len;
+    for (u32 k = 0; k < len; k++)
+        if (fop_equal(op, vals[d[h + k]], x)) { found = k; break; }
+    if (found < len) {
+        for (u32 k = found; k > 0; k--) d[h + k] = d[h + k - 1];
+        h++;
+        len--;
+    }
+    if (len == 0) return false;
+    *front = vals[d[h]];
+    return true;
+}
+
 }  // namespace shd

@@ -1,6 +1,7 @@
 // sh_having.cpp — the `having` program of a batch-window query: the type-checking compiler behind
 // sh_having_check and sh_query_set_having, and the per-query state (sh_having.h). The evaluation is in
-// sh_having_kernels.hip, routed from run_closed (sh_window.cpp) and sc_rows (sh_stream_current.cpp).
+// sh_having_kernels.hip, routed from run_closed (sh_window.cpp) and sc_rows / sc_expire_pending
+// (sh_stream_current.cpp).
 #include "sh_having.h"
 
 #include <string>
@@ -62,8 +63,14 @@ int having_compile(const sh_query_desc* d, const sh_filter_op* ops, int32_t n_op
     if (d->window != SH_WIN_LENGTH_BATCH && d->window != SH_WIN_TIME_BATCH && d->window != SH_WIN_EXT_TIME_BATCH)
         return sh_fail(SH_ERR_UNSUPPORTED, std::string("having on ") + window_name(d->window) +
                                                ": the GPU runs having on lengthBatch, timeBatch and externalTimeBatch");
-    if (d->expired_on != 0)
-        return sh_fail(SH_ERR_UNSUPPORTED, "having with expired / all-events output (current-events output only)");
+    // expired rows show the aggregates after every removal: the stream.current.event forms keep the whole
+    // window in the pending buffer and walk it again (k_hvx_walk); the plain windows would have to carry
+    // the previous batch's events across calls
+    if (d->expired_on != 0 && !(d->stream_current && (d->window == SH_WIN_LENGTH_BATCH || d->window == SH_WIN_TIME_BATCH)))
+        return sh_fail(SH_ERR_UNSUPPORTED,
+                       "having with expired / all-events output on this window: it runs on lengthBatch(L, true) and "
+                       "timeBatch(T, true) (stream.current.event); the other batch windows run it with current-events "
+                       "output only");
     if (d->partition_col >= 0) return sh_fail(SH_ERR_UNSUPPORTED, "having in a partitioned query (partition lanes)");
     if (d->n_group_by > 0 && WideKeys::needed(d->n_group_by, d->group_by, d->col_types))
         return sh_fail(SH_ERR_UNSUPPORTED, "having with a group-by the library interns (wide keys)");

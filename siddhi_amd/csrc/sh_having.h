@@ -48,6 +48,36 @@ void launch_hv_walk(hipStream_t s, int kind, i64 M, const u32* pos, const u32* s
                     const u64* pend_vals, i64 pend_cap, const u32* pend_pos, AggPlan ap, KeyTable kt, KeyPlan kp,
                     HavingProg hp, u32* ghead, u64* sval, u32* slast);
 
+// Expired / all-events output of lengthBatch(L, true) / timeBatch(T, true) (sh_stream_current.cpp sc_rows,
+// sc_expire_pending). launch_hvx_walk is launch_hv_walk plus, for a run whose window closes in the call
+// (its window index in skey's high word below nb), the ordered remove pass: xhead flags the entry of the
+// run's first passing removal, xlast / xval / xnul (at that entry) give the last passing removal's entry,
+// values and null flags, xrun (at the run's first sorted entry) the head's entry or 0xFFFFFFFF. The
+// current role's flags are kept only with cur_on. dq: n_fields * M entry numbers, the min / max deques
+// (NULL when the plan has no min or max). xhead must be zero on entry.
+void launch_hvx_walk(hipStream_t s, int kind, i64 M, const u32* pos, const u32* starts, const u32* idx, const i64* chunk,
+                     const u64* skey, int nb, int cur_on, const u64* pend_vals, i64 pend_cap, const u32* pend_pos,
+                     AggPlan ap, KeyTable kt, KeyPlan kp, HavingProg hp, u32* ghead, u64* sval, u32* slast, u32* xhead,
+                     u64* xval, unsigned char* xnul, u32* xlast, u32* xrun, u32* dq);
+// lengthBatch: launch_scx_count's rows per chunk and key rank of a batch's first event, over passing heads
+// (xpre: xhead scanned)
+void launch_hvx_count(hipStream_t s, i64 M, i64 n_old, const i64* pcb, const u64* skey, const u64* skey2, const u32* idx2,
+                      const u32* xpre, const u32* xrun, const u32* ghead, u32* rows, i64* rank_e);
+// the expired rows of the passing heads. mode 0 lengthBatch (clk: the sends' clocks), 1 timeBatch (clk: the
+// window starts' clocks), 2 one flush at `now` (row = xpre, no chunk columns)
+void launch_hvx_expired(hipStream_t s, i64 M, i64 n_old, const i64* pcb, const u64* skey, const u32* xhead,
+                        const u32* xpre, const u32* xlast, const u64* xval, const unsigned char* xnul, const u32* base,
+                        const i64* rank_e, const i64* send, const i64* clk, i64 now, const u32* pend_pos,
+                        const u64* pend_gidx, KeyTable kt, KeyPlan kp, int na, int mode, i64 T, i64* out_ts, i64* out_keys,
+                        u64* out_vals, unsigned char* out_nulls, unsigned char* out_exp, i64* out_rep, i64* out_chunk,
+                        i64* out_send);
+// lengthBatch: the passing current rows (launch_scx_rows' current half over ghead)
+void launch_hvx_current(hipStream_t s, i64 M, i64 n_old, const i64* pcb, const u64* skey, const u32* xpre,
+                        const u32* ghead, const u32* base, const i64* rank_e, const u64* sval, const i64* send,
+                        const i64* pend_ts, const u64* pend_gidx, KeyTable kt, KeyPlan kp, int na, i64 T, i64* out_ts,
+                        i64* out_keys, u64* out_vals, unsigned char* out_nulls, unsigned char* out_exp, i64* out_rep,
+                        i64* out_chunk, i64* out_send);
+
 }  // namespace shd
 
 // Per-query state: the compiled program (configuration, not state: snapshots neither store nor

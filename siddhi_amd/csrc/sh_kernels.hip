@@ -1951,8 +1951,7 @@ void launch_sc_send_last(hipStream_t s, const i64* ts, i64 N, i64 send_size, i64
 // selector groups that chunk by key, so batch w's keys show their empty state (count 0, the others
 // null) at their first-occurrence position, each with ts = the chunk's clock and the representative
 // event of the key's last event in w; with `all events` the new event's own row replaces its key's
-// expired row (LinkedHashMap.put) or follows them.
-__device__ __forceinline__ i64 sc_wstart(i64 w, i64 n_old, const i64* pcb) { return w == 0 ? 0 : n_old + pcb[w - 1]; }
+// expired row (LinkedHashMap.put) or follows them. (sc_wstart: sh_device.h)
 
 // fe[m] = 1 at the first entry (stream order) of every (window, key) run; lastidx[first] = its last entry
 __global__ __launch_bounds__(kBlock) void k_scx_first(i64 M, const u32* __restrict__ hd, const u32* __restrict__ pos,
@@ -2194,10 +2193,21 @@ void launch_scxt_rows(hipStream_t s, i64 M, i64 n_old, const i64* pcb, int nb, c
     hipLaunchKernelGGL(k_scx_expired, dim3(sc_grid(M)), dim3(kBlock), 0, s, M, n_old, pcb, nb, skey, fe, fpre, lastidx,
                        base, (const i64*)nullptr, send, (const i64*)nullptr, bclk, pend_gidx, kt, kp, ap, 0, 1, T,
                        out_ts, out_keys, out_vals, out_nulls, out_exp, out_rep, out_chunk, out_send);
-    if (cur_on && M > n_old)
-        hipLaunchKernelGGL(k_scxt_current, dim3(sc_grid(M - n_old)), dim3(kBlock), 0, s, M, n_old, pcb, nb, skey, fpre,
-                           ghead, base, slast, sval, chunk, send, pend_ts, pend_gidx, kt, kp, ap.n, T, out_ts, out_keys,
-                           out_vals, out_nulls, out_exp, out_rep, out_chunk, out_send);
+    if (cur_on)
+        launch_scxt_current(s, M, n_old, pcb, nb, skey, fpre, ghead, base, slast, sval, chunk, send, pend_ts, pend_gidx,
+                            kt, kp, ap.n, T, out_ts, out_keys, out_vals, out_nulls, out_exp, out_rep, out_chunk, out_send);
+}
+
+// the current half alone (fpre: the scanned flags of whatever entries head the closing windows' expired rows)
+void launch_scxt_current(hipStream_t s, i64 M, i64 n_old, const i64* pcb, int nb, const u64* skey, const u32* fpre,
+                         const u32* ghead, const u32* base, const u32* slast, const u64* sval, const i64* chunk,
+                         const i64* send, const i64* pend_ts, const u64* pend_gidx, KeyTable kt, KeyPlan kp, int na, i64 T,
+                         i64* out_ts, i64* out_keys, u64* out_vals, unsigned char* out_nulls, unsigned char* out_exp,
+                         i64* out_rep, i64* out_chunk, i64* out_send) {
+    if (T <= 0 || M <= n_old) return;
+    hipLaunchKernelGGL(k_scxt_current, dim3(sc_grid(M - n_old)), dim3(kBlock), 0, s, M, n_old, pcb, nb, skey, fpre, ghead,
+                       base, slast, sval, chunk, send, pend_ts, pend_gidx, kt, kp, na, T, out_ts, out_keys, out_vals,
+                       out_nulls, out_exp, out_rep, out_chunk, out_send);
 }
 
 void launch_scx_pending_rows(hipStream_t s, i64 M, const u32* fe, const u32* fpre, const u32* lastidx,

@@ -417,6 +417,9 @@ struct sh_query {
     DevBuf sc_pcb, sc_skey, sc_skey2, sc_idx, sc_idx2, sc_chunk, sc_send, sc_hd, sc_pos, sc_starts, sc_tmp, sc_ghead,
         sc_pre, sc_sval, sc_slast, sc_ochunk, sc_osend, sc_sl, sc_sort, scx_fe, scx_fpre, scx_last, scx_rows, scx_rank,
         scx_clk;
+    // ... of a having program's remove pass (expired output): each run's head, the rows' values and nulls
+    // at the heads, the min / max deques (scx_fe / scx_fpre / scx_last hold the passing heads instead)
+    DevBuf hvx_run, hvx_val, hvx_nul, hvx_dq;
     PinnedBuf sc_h, sc_hp, sc_ho, h_small_sc;
     // `output [all|first|last] every N events` (sh_rate.cpp): the limiter's state across calls
     struct Rate {

@@ -134,15 +134,45 @@ static int upload_i64(sh_query* q, PinnedBuf& h, DevBuf& d, int n, F value) {
     return SH_OK;
 }
 
+static bool plan_has_minmax(const AggPlan& ap) {
+    for (int j = 0; j < ap.n_fields; j++)
+        if (ap.fop[j] >= FOP_MIN_I) return true;
+    return false;
+}
+
+// Scratch of a having program's remove pass over M entries (k_hvx_walk): the passing heads (scx_fe,
+// zeroed; scx_fpre for their scan; scx_last the last passing removal), each run's head, the rows' values
+// and null flags, and — only for a plan with a min or max — the deques: a run of n entries needs at most
+// n slots per field, at its own offset in the sorted order.
+static int reserve_remove_pass(sh_query* q, int64_t M) {
+    const size_t na = std::max(q->ap.n, 1);
+    for (DevBuf* d : {&q->scx_fe, &q->scx_fpre}) RCHK(d->reserve((size_t)(M + 1) * 4, false));
+    for (DevBuf* d : {&q->scx_last, &q->hvx_run}) RCHK(d->reserve((size_t)std::max<int64_t>(M, 1) * 4, false));
+    RCHK(q->hvx_val.reserve(na * std::max<int64_t>(M, 1) * 8, false));
+    RCHK(q->hvx_nul.reserve(na * std::max<int64_t>(M, 1), false));
+    if (plan_has_minmax(q->ap)) RCHK(q->hvx_dq.reserve((size_t)q->ap.n_fields * std::max<int64_t>(M, 1) * 4, false));
+    HIPCHK(hipMemsetAsync(q->scx_fe.p, 0, (size_t)(M + 1) * 4, q->ctx->stream));
+    return SH_OK;
+}
+
 // One thread per run folds its entries in event order, timed between ev_agg0 and ev_agg1: the head flag of
 // each (chunk, key) group among the entries from n_old on, its last entry and the running values there.
 // A having program (sh_having.h) is evaluated after every entry: first / last passing entry per group.
 // heads == false: every new entry is a chunk of its own, so a head, and no flags are kept.
-static int walk_runs(sh_query* q, int64_t M, int64_t n_old, bool heads) {
+// closing >= 0 (a program with expired output; reserve_remove_pass came first): the runs of the windows
+// below `closing` close in this call and are walked a second time with the remove forms (k_hvx_walk).
+static int walk_runs(sh_query* q, int64_t M, int64_t n_old, bool heads, int closing = -1) {
     hipStream_t s = q->ctx->stream;
     if (heads) HIPCHK(hipMemsetAsync(q->sc_ghead.p, 0, (size_t)(M + 1) * 4, s));
     HIPCHK(hipEventRecord(q->ev_agg0, s));
-    if (q->hv.on)
+    if (q->hv.on && closing >= 0)
+        launch_hvx_walk(s, q->hv.kind, M, q->sc_pos.as<u32>(), q->sc_starts.as<u32>(), q->sc_idx2.as<u32>(),
+                        q->sc_chunk.as<int64_t>(), q->sc_skey.as<u64>(), closing, q->d.current_on ? 1 : 0,
+                        q->pend_vals.as<u64>(), q->pend_cap, q->pend_pos.as<u32>(), q->ap, q->kt.dev(), q->kp, q->hv.prog,
+                        q->sc_ghead.as<u32>(), q->sc_sval.as<u64>(), q->sc_slast.as<u32>(), q->scx_fe.as<u32>(),
+                        q->hvx_val.as<u64>(), q->hvx_nul.as<unsigned char>(), q->scx_last.as<u32>(), q->hvx_run.as<u32>(),
+                        plan_has_minmax(q->ap) ? q->hvx_dq.as<u32>() : nullptr);
+    else if (q->hv.on)
         launch_hv_walk(s, q->hv.kind, M, q->sc_pos.as<u32>(), q->sc_starts.as<u32>(), q->sc_idx2.as<u32>(),
                        q->sc_chunk.as<int64_t>(), q->pend_vals.as<u64>(), q->pend_cap, q->pend_pos.as<u32>(), q->ap,
                        q->kt.dev(), q->kp, q->hv.prog, q->sc_ghead.as<u32>(), q->sc_sval.as<u64>(), q->sc_slast.as<u32>());
@@ -351,7 +381,11 @@ int sc_rows(sh_query* q, const sh_batch* b, const std::vector<Bound>& bounds, in
     // (the slot count here leaves out the sentinel key's slot, mask + 1, which hv_closed counts)
     const unsigned end_bit = xs || xt ? 64 : pack_keys(q, M, q->kt.size_, nb);
     RCHK(sort_runs(q, M, end_bit, "stream.current"));
-    RCHK(walk_runs(q, M, n_old, !all_heads));
+    // (a program with expired output: the closing windows' runs are walked again with the remove forms, and
+    // the expired rows are those of the passing heads — scx_fe — instead of every key of a closing window)
+    const bool hvx = hv && (xs || xt);
+    if (hvx) RCHK(reserve_remove_pass(q, M));
+    RCHK(walk_runs(q, M, n_old, !all_heads, hvx ? nb : -1));
     const int64_t nn = M - n_old;
     // the sends' playback clocks: TimestampGeneratorImpl only moves forward (prefix max of send-last ts);
     // a sharded owner's records (one send each) carry their global send's clock instead
@@ -395,9 +429,16 @@ int sc_rows(sh_query* q, const sh_batch* b, const std::vector<Bound>& bounds, in
         RCHK(q->scx_rows.reserve((size_t)(nn + 2) * 4, false));
         RCHK(q->scx_rank.reserve((size_t)std::max<int64_t>(nn, 1) * 8, false));
         RCHK(q->scx_clk.reserve((size_t)n_sends * 8, false));
-        RCHK(first_entries(q, M));
+        if (hvx)
+            HIPCHK(hipMemcpyAsync(q->scx_fpre.p, q->scx_fe.p, (size_t)(M + 1) * 4, hipMemcpyDeviceToDevice, s));
+        else
+            RCHK(first_entries(q, M));
         launch_scan_sum_large_u32(s, q->scx_fpre.as<u32>(), M + 1, q->sc_tmp.as<int64_t>());
-        if (xs)
+        if (xs && hvx)
+            launch_hvx_count(s, M, n_old, q->sc_pcb.as<int64_t>(), q->sc_skey.as<u64>(), q->sc_skey2.as<u64>(),
+                             q->sc_idx2.as<u32>(), q->scx_fpre.as<u32>(), q->hvx_run.as<u32>(), q->sc_ghead.as<u32>(),
+                             q->scx_rows.as<u32>(), q->scx_rank.as<int64_t>());
+        else if (xs)
             launch_scx_count(s, M, n_old, q->sc_pcb.as<int64_t>(), q->sc_skey.as<u64>(), q->sc_skey2.as<u64>(),
                              q->sc_idx2.as<u32>(), q->scx_fpre.as<u32>(), cur_on, 1, q->scx_rows.as<u32>(),
                              q->scx_rank.as<int64_t>());
@@ -421,7 +462,33 @@ int sc_rows(sh_query* q, const sh_batch* b, const std::vector<Bound>& bounds, in
     }
     RCHK(reserve_chunk_rows(q, T));
     if (q->given) RCHK(q->out_order.reserve((size_t)std::max<int64_t>(T, 1) * 8, false));
-    if (xs) {
+    if (hvx) {
+        // the expired rows of the passing heads, with their values and nulls; the current rows that pass
+        launch_hvx_expired(s, M, n_old, q->sc_pcb.as<int64_t>(), q->sc_skey.as<u64>(), q->scx_fe.as<u32>(),
+                           q->scx_fpre.as<u32>(), q->scx_last.as<u32>(), q->hvx_val.as<u64>(),
+                           q->hvx_nul.as<unsigned char>(), q->scx_rows.as<u32>(), q->scx_rank.as<int64_t>(),
+                           q->sc_send.as<int64_t>(), q->scx_clk.as<int64_t>(), 0, q->pend_pos.as<u32>(),
+                           q->pend_gidx.as<u64>(), q->kt.dev(), q->kp, q->ap.n, xs ? 0 : 1, T, q->out_ts.as<int64_t>(),
+                           q->out_keys.as<int64_t>(), q->out_vals.as<u64>(), q->out_nulls.as<unsigned char>(),
+                           q->out_expired.as<unsigned char>(), q->out_rep.as<int64_t>(), q->sc_ochunk.as<int64_t>(),
+                           q->sc_osend.as<int64_t>());
+        if (cur_on && xs)
+            launch_hvx_current(s, M, n_old, q->sc_pcb.as<int64_t>(), q->sc_skey.as<u64>(), q->scx_fpre.as<u32>(),
+                               q->sc_ghead.as<u32>(), q->scx_rows.as<u32>(), q->scx_rank.as<int64_t>(),
+                               q->sc_sval.as<u64>(), q->sc_send.as<int64_t>(), q->pend_ts.as<int64_t>(),
+                               q->pend_gidx.as<u64>(), q->kt.dev(), q->kp, q->ap.n, T, q->out_ts.as<int64_t>(),
+                               q->out_keys.as<int64_t>(), q->out_vals.as<u64>(), q->out_nulls.as<unsigned char>(),
+                               q->out_expired.as<unsigned char>(), q->out_rep.as<int64_t>(),
+                               q->sc_ochunk.as<int64_t>(), q->sc_osend.as<int64_t>());
+        else if (cur_on)
+            launch_scxt_current(s, M, n_old, q->sc_pcb.as<int64_t>(), nb, q->sc_skey.as<u64>(), q->scx_fpre.as<u32>(),
+                                q->sc_ghead.as<u32>(), q->scx_rows.as<u32>(), q->sc_slast.as<u32>(), q->sc_sval.as<u64>(),
+                                q->sc_chunk.as<int64_t>(), q->sc_send.as<int64_t>(), q->pend_ts.as<int64_t>(),
+                                q->pend_gidx.as<u64>(), q->kt.dev(), q->kp, q->ap.n, T, q->out_ts.as<int64_t>(),
+                                q->out_keys.as<int64_t>(), q->out_vals.as<u64>(), q->out_nulls.as<unsigned char>(),
+                                q->out_expired.as<unsigned char>(), q->out_rep.as<int64_t>(),
+                                q->sc_ochunk.as<int64_t>(), q->sc_osend.as<int64_t>());
+    } else if (xs) {
         launch_scx_rows(s, M, n_old, q->sc_pcb.as<int64_t>(), nb, q->sc_skey.as<u64>(), q->scx_fe.as<u32>(),
                         q->scx_fpre.as<u32>(), q->scx_last.as<u32>(), q->scx_rows.as<u32>(), q->scx_rank.as<int64_t>(),
                         q->sc_sval.as<u64>(), q->sc_send.as<int64_t>(), q->scx_clk.as<int64_t>(),
@@ -511,8 +578,34 @@ int sc_expire_pending(sh_query* q, int64_t now, bool host_out) {
     launch_sc_keys(s, M, M, q->sc_pcb.as<int64_t>(), 0, q->pend_pos.as<u32>(), q->pend_gidx.as<u64>(), 0, 0, 0,
                    q->sc_skey.as<u64>(), q->sc_idx.as<u32>(), q->sc_chunk.as<int64_t>(), q->sc_send.as<int64_t>());
     RCHK(sort_runs(q, M, 64, "stream.current"));
-    RCHK(first_entries(q, M));
     int64_t T = 0;
+    if (q->hv.on) {
+        // a program: every run folds (no entry is of this call, so none is tested as CURRENT), then the
+        // remove pass; the rows are the passing heads', in arrival order
+        RCHK(reserve_walk(q, M));
+        RCHK(reserve_remove_pass(q, M));
+        RCHK(walk_runs(q, M, M, true, 1));
+        HIPCHK(hipMemcpyAsync(q->scx_fpre.p, q->scx_fe.p, (size_t)(M + 1) * 4, hipMemcpyDeviceToDevice, s));
+        RCHK(scan_total(q, q->scx_fpre.as<u32>(), M + 1, &T));
+        add_walk_ms(q);
+        RCHK(reserve_out_rows(q, T));
+        launch_hvx_expired(s, M, M, nullptr, nullptr, q->scx_fe.as<u32>(), q->scx_fpre.as<u32>(), q->scx_last.as<u32>(),
+                           q->hvx_val.as<u64>(), q->hvx_nul.as<unsigned char>(), nullptr, nullptr, nullptr, nullptr, now,
+                           q->pend_pos.as<u32>(), q->pend_gidx.as<u64>(), q->kt.dev(), q->kp, q->ap.n, 2, T,
+                           q->out_ts.as<int64_t>(), q->out_keys.as<int64_t>(), q->out_vals.as<u64>(),
+                           q->out_nulls.as<unsigned char>(), q->out_expired.as<unsigned char>(), q->out_rep.as<int64_t>(),
+                           nullptr, nullptr);
+        HIPCHK(hipGetLastError());
+        const FlushVecs fl = flush_vecs(q, host_out);
+        fl.offsets.assign(1, 0);
+        fl.clocks.clear();
+        if (T) {
+            fl.offsets.push_back(T);
+            fl.clocks.push_back(now);
+        }
+        return rows_out(q, T, host_out, false);
+    }
+    RCHK(first_entries(q, M));
     RCHK(scan_total(q, q->scx_fpre.as<u32>(), M + 1, &T));
     RCHK(reserve_out_rows(q, T));
     launch_scx_pending_rows(s, M, q->scx_fe.as<u32>(), q->scx_fpre.as<u32>(), q->scx_last.as<u32>(),

@@ -1402,6 +1402,13 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
             }
             std::sort(bounds.begin(), bounds.end(), [](const Bound& a, const Bound& c) { return a.idx < c.idx; });
         }
+        // lengthBatch(L, true) with expired output: a batch closes in the chunk of the event that STARTS the
+        // next one (count == length + 1, LengthBatchWindowProcessor.java:249-266). k_boundaries' W rises at the
+        // first event after the L-th passing one, whether it passes or not; when nothing passes after it in
+        // this push, that last boundary has no chunk yet — the full batch stays queued, and the next push's
+        // first passing event closes it and carries its expired rows.
+        if (q->d.stream_current && q->d.expired_on && q->d.window == SH_WIN_LENGTH_BATCH && !q->given)
+            while (!bounds.empty() && bounds.back().pcb >= info.total_pass) bounds.pop_back();
         if (q->xt_replace) {  // (the windows start at new events: stream index = seq0 + combined index - queued)
             RCHK(xr_trim(q));  // (what earlier calls left, so a call failing after this point leaves few)
             for (auto& bd : bounds) q->xr_starts.emplace_back(seq0 + std::max<int64_t>(0, bd.idx - q->n_pend), bd.W);
