@@ -215,7 +215,8 @@ size_t scan_blocks_first_bytes(int nblk);
 void launch_scan_blocks(hipStream_t s, i64* blk_pass, i64* blk_tl, i64* blk_first, int nblk, const i64* ts,
                         WinParams wp, PushInfo* info, i64* blk_xm = nullptr, ColSet cols = ColSet{});
 // sorted: the single-pass form for non-decreasing timestamps (timeBatch with nextEmitTime known); it
-// also scans blk_pass (nblk + 1 entries, the last zeroed) with scan_tmp and fixes the boundaries
+// also scans blk_pass (nblk + 1 entries, the last zeroed) with scan_tmp and fixes the boundaries — unless
+// the query has no filter: every event passes, and the kernel writes the prefixes and the info itself
 void launch_boundaries(hipStream_t s, const i64* ts, ColSet cols, FilterProg f, WinParams wp,
                        i64* blk_pass_pre, const i64* blk_tl_pre, PushInfo* info, Bound* bounds,
                        int max_bounds, int nblk, KeyPlan kp, KeyTable kt, u32* new_pos, const i64* blk_xm_pre = nullptr,

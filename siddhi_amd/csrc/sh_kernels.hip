@@ -245,7 +245,9 @@ void launch_scan_blocks(hipStream_t s, i64* blk_pass, i64* blk_tl, i64* blk_firs
 // checks that ts never decreases across its events and into the next tile's first event; a tile
 // that finds a decrease sets PushInfo.unsorted and the host redoes the window assignment with the
 // prefix passes. The tile's passing-event count goes to blk_pass[tile] and each boundary records
-// its tile and in-tile count; k_fix_bounds adds the scanned tile prefixes afterwards.
+// its tile and in-tile count; k_fix_bounds adds the scanned tile prefixes afterwards. Without a filter
+// (FK == 0) every event passes: tile t's prefix is t * kTile and the totals are known, so the kernel
+// writes push-relative counts, the prefixes and PushInfo itself and nothing follows it.
 template <bool EXT, int FK, bool SORTED>
 __global__ __launch_bounds__(kBlock) void k_boundaries(const i64* __restrict__ ts, ColSet cols, FilterProg f,
                                                       WinParams wp, i64* blk_pass_pre, const i64* blk_tl_pre,
@@ -322,9 +324,29 @@ __global__ __launch_bounds__(kBlock) void k_boundaries(const i64* __restrict__ t
     }
     i64 pcb, pm = INT64_MIN;
     if (SORTED) {
-        i64 tot_c;
-        pcb = block_excl_scan(cnt, SumOp(), 0, &tot_c);  // in-tile: the tile prefix is added later
-        if (threadIdx.x == 0) blk_pass_pre[tile] = tot_c;
+        if (FK == 0) {
+            // no filter: every in-range event passes, so the tile prefixes and the push totals are known
+            // in closed form — no scan of the tile counts and no k_fix_bounds behind this kernel.
+            // blk_pass_pre and PushInfo end up exactly as that chain leaves them.
+            pcb = min(base, wp.N);  // push-relative at once
+            if (threadIdx.x == 0) {
+                blk_pass_pre[tile] = (i64)tile * kTile;
+                if (tile == (int)gridDim.x - 1) {
+                    blk_pass_pre[gridDim.x] = wp.N;
+                    info->total_pass = wp.N;
+                    info->max_tl = ts[wp.N - 1];
+                    info->first_pass = wp.N ? 0 : INT64_MAX;
+                    info->E0 = wp.E0;
+                    info->e0_valid = wp.e0_valid;
+                    info->first_clk = INT64_MIN;
+                    info->max_xm = INT64_MIN;
+                }
+            }
+        } else {
+            i64 tot_c;
+            pcb = block_excl_scan(cnt, SumOp(), 0, &tot_c);  // in-tile: the tile prefix is added later
+            if (threadIdx.x == 0) blk_pass_pre[tile] = tot_c;
+        }
         bool down = false;
 #pragma unroll
         for (int i = 0; i + 1 < kItems; i++) down |= base + i + 1 < wp.N && t[i + 1] < t[i];
@@ -382,8 +404,8 @@ __global__ __launch_bounds__(kBlock) void k_boundaries(const i64* __restrict__ t
             if (k < max_bounds) {
                 Bound b;
                 b.idx = wp.n_pend + e; b.W = W; b.clock = clk; b.clock_prev = clock_prev; b.pcb = pcb;
-                // (SORTED: pcb is in-tile until k_fix_bounds; externalTimeBatch: the attribute max M at
-                // the closing event, the expired rows' timestamp)
+                // (SORTED with a filter: pcb is in-tile until k_fix_bounds; externalTimeBatch: the attribute
+                // max M at the closing event, the expired rows' timestamp)
                 b.pad = SORTED ? tile : ext ? M : 0;
                 bounds[k] = b;
             }
@@ -450,8 +472,9 @@ void launch_boundaries(hipStream_t s, const i64* ts, ColSet cols, FilterProg f, 
     else if (fk == 1) SH_BOUNDS(false, 1, false);
     else SH_BOUNDS(false, 2, false);
 #undef SH_BOUNDS
-    if (sorted) {
+    if (sorted && fk != 0) {
         // blk_pass[nblk] was zeroed with the info block: the scan leaves the total there
+        // (no filter: k_boundaries wrote the prefixes, the total and the push info itself)
         launch_scan_sum_large(s, blk_pass_pre, nblk + 1, scan_tmp);
         hipLaunchKernelGGL(k_fix_bounds, dim3(1), dim3(kBlock), 0, s, bounds, max_bounds, blk_pass_pre, nblk, ts, wp,
                            info);

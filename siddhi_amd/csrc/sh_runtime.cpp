@@ -183,8 +183,10 @@ extern "C" int sh_init(int32_t device, sh_ctx** out) {
     c->num_cus = prop.multiProcessorCount;
     c->max_lds = (int)prop.sharedMemPerBlock;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) {
+        hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess ||
+        hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess) {
         if (c->stream) (void)hipStreamDestroy(c->stream);
+        if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
         delete c;
         return sh_fail(SH_ERR_DEVICE, "hipStreamCreate failed");
     }
@@ -196,8 +198,10 @@ extern "C" int sh_ctx_destroy(sh_ctx* c) {
     if (!c) return SH_OK;
     (void)hipStreamSynchronize(c->stream);
     (void)hipStreamSynchronize(c->copy_stream);
+    (void)hipStreamSynchronize(c->side_stream);
     (void)hipStreamDestroy(c->stream);
     (void)hipStreamDestroy(c->copy_stream);
+    (void)hipStreamDestroy(c->side_stream);
     delete c;
     return SH_OK;
 }
@@ -230,6 +234,8 @@ Tuning Tuning::from_env() {
     t.pl_sort = !getenv("SH_PL_SORT") || on("SH_PL_SORT");
     if (getenv("SH_AGG_BAND_ROWS")) t.agg_band_rows = atoi(getenv("SH_AGG_BAND_ROWS"));
     t.slx_wave = !getenv("SH_SLX_WAVE") || on("SH_SLX_WAVE");
+    // a large push's independent small kernels beside the big passes; SH_SIDE_STREAM=0: one stream
+    t.side_stream = !getenv("SH_SIDE_STREAM") || on("SH_SIDE_STREAM");
     return t;
 }
 

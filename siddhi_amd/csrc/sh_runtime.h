@@ -21,6 +21,9 @@ struct sh_ctx {
     int max_lds = 0;
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;  // H2D staging of host batches (sh_stage), beside the compute stream
+    // a large batch-window push's small kernels that do not depend on their predecessor run here, beside
+    // the big passes on `stream` (ordered by events; idle again before the push returns: DESIGN.md §4)
+    hipStream_t side_stream = nullptr;
 };
 
 int sh_fail(int code, const std::string& msg);
@@ -226,7 +229,9 @@ struct SlidingImpl;
 // A/B switches of the measured alternatives, read from the environment once per query,
 // when it is created, so a process can run queries with different settings side by side:
 // SH_DIRECT_POS=1, SH_PART_KEYS=1024, SH_NO_ASYNC_SMALL=1, SH_SL_RECORDS_SEQ=0/1, SH_AGG_BAND_ROWS=n,
+// SH_SIDE_STREAM=0 (a large push's bookkeeping back on the one stream, compaction in place)
 struct Tuning {
+    bool side_stream = true;
     bool direct_pos = false, part_keys_1024 = false, no_async_small = false, sl_records_seq = false;
     bool pl_sort = true;   // partitioned lengthBatch keyed by the partition on the sorted lanes (lane 3)
     bool slx_wave = true;     // expired / all-events sliding replay with a wave per key (k_slx_wkey); SH_SLX_WAVE=0: a lane per key
@@ -315,6 +320,13 @@ struct sh_query {
     int64_t seq = 0;  // stream index of the next event pushed (sh_out.rep numbering)
     DevBuf pend_pos, pend_ts, pend_vals;
     DevBuf pend_tmp;  // staging of pending_to_front's overlapping moves (kept: no allocation per push)
+    // spare set of the pending buffers: a large push that closes a window compacts its open window's
+    // events into it on the side stream while the fold and the emission still read the old entries; the
+    // two sets change places after the push's final wait (push_core)
+    DevBuf sp_pos, sp_ts, sp_vals, sp_gidx;
+    int64_t sp_cap = 0;
+    // this push runs its independent small kernels on the context's side stream (set by push_core)
+    bool side_push = false;
     // scratch
     DevBuf blk_pass, blk_tl, blk_first, blk_xm, info, bounds, segs, seg_rows, rows, counters, out_ts, out_keys, out_vals,
         out_nulls, out_expired, out_rep, blk_cnt;
@@ -376,6 +388,9 @@ struct sh_query {
     hipEvent_t ev_srt0 = nullptr, ev_srt1 = nullptr;
     bool srt_timed = false;
     hipEvent_t ev_mid = nullptr;  // the push info and boundaries are on the host (work queued after it runs on)
+    // side-stream ordering of a push: pending tiles counted (side), multisplit offsets scanned (main),
+    // segment offsets and bitmap ready (side), open window compacted into the spare buffers (side)
+    hipEvent_t ev_cnt = nullptr, ev_ms_off = nullptr, ev_seg = nullptr, ev_cmp = nullptr;
     sh_stats stats{};
     int64_t agg_bytes = 0;
     // per flush of the last push: window number (internal use by the aggregation root)
@@ -513,7 +528,8 @@ int hv_closed(sh_query* q, const std::vector<shd::Segment>& segs, const std::vec
 // ... and what they need of sh_window.cpp: the push's passing events appended to the pending entries
 // [n_old, M); the closed windows' segment list on the device (q->segs)
 int append_pending(sh_query* q, const sh_batch* b, int64_t n_old, int64_t M);
-int upload_segments(sh_query* q, const std::vector<shd::Segment>& segs);
+// (stream: the context's compute stream unless given)
+int upload_segments(sh_query* q, const std::vector<shd::Segment>& segs, hipStream_t stream = nullptr);
 
 // the filter restricted to partition key `key` (R12): base AND (pcol == key)
 int partition_filter(const FilterProg& base, int pcol, int ptype, int64_t key, FilterProg* out);

@@ -110,6 +110,40 @@ static int grow_pending(sh_query* q, int64_t need, int64_t keep) {
     return SH_OK;
 }
 
+// The spare pending set sized for `need` entries. Nothing in it is kept and nothing queued reads it
+// (the push before the last swap has finished), so growth copies nothing.
+static int grow_spare(sh_query* q, int64_t need) {
+    if (need <= q->sp_cap) return SH_OK;
+    // Twice the largest of the need and the two sets: the sets change places at every push that closes a
+    // window, so the smaller one would otherwise grow again whenever a large open window falls on it
+    // (x1.5 steps per set kept growing for ~10 pushes at C2's size, each a free + allocate of four
+    // blocks in the middle of a push; doubled, both sets are large enough after the second push)
+    int64_t ncap = 2 * std::max<int64_t>(need, std::max(q->pend_cap, q->sp_cap));
+    ncap = std::max<int64_t>(ncap, 4096);
+    for (DevBuf* d : {&q->sp_pos, &q->sp_ts, &q->sp_vals, &q->sp_gidx}) {
+        if (d->p) (void)hipFree(d->p);
+        d->p = nullptr;
+        d->cap = d->used = 0;
+    }
+    q->sp_cap = 0;
+    RCHK(q->sp_pos.reserve(ncap * 4, false));
+    RCHK(q->sp_ts.reserve(ncap * 8, false));
+    RCHK(q->sp_vals.reserve(std::max(1, q->ap.n_vcols) * ncap * 8, false));
+    RCHK(q->sp_gidx.reserve(ncap * 8, false));
+    q->sp_cap = ncap;
+    return SH_OK;
+}
+
+// the pending set and its spare change places (no queued work reads either: after a push's final wait)
+static void swap_pending(sh_query* q) {
+    auto sw = [](DevBuf& a, DevBuf& b) { std::swap(a.p, b.p); std::swap(a.cap, b.cap); std::swap(a.used, b.used); };
+    sw(q->pend_pos, q->sp_pos);
+    sw(q->pend_ts, q->sp_ts);
+    sw(q->pend_vals, q->sp_vals);
+    sw(q->pend_gidx, q->sp_gidx);
+    std::swap(q->pend_cap, q->sp_cap);
+}
+
 static int query_create(sh_ctx* ctx, const sh_query_desc* d, const KeyPlan* kp_override, sh_query** out);
 int query_set_partition(sh_query* q, int64_t key);
 
@@ -404,6 +438,8 @@ static int query_create(sh_ctx* ctx, const sh_query_desc* d, const KeyPlan* kp_o
     (void)hipEventCreate(&q->ev_push0); (void)hipEventCreate(&q->ev_push1);
     (void)hipEventCreate(&q->ev_agg0); (void)hipEventCreate(&q->ev_agg1);
     (void)hipEventCreateWithFlags(&q->ev_mid, hipEventDisableTiming);
+    for (hipEvent_t* e : {&q->ev_cnt, &q->ev_ms_off, &q->ev_seg, &q->ev_cmp})
+        (void)hipEventCreateWithFlags(e, hipEventDisableTiming);
     *out = q;
     return SH_OK;
 }
@@ -468,12 +504,12 @@ static WinParams base_win_params(const sh_query* q, int64_t send_size, int64_t N
 
 // the segment list goes up from pinned memory (an async copy from pageable memory may read it after
 // the caller returned)
-int upload_segments(sh_query* q, const std::vector<Segment>& segs) {
+int upload_segments(sh_query* q, const std::vector<Segment>& segs, hipStream_t stream) {
     const size_t bytes = segs.size() * sizeof(Segment);
     RCHK(q->h_up.reserve(bytes));
     RCHK(q->segs.reserve(bytes, false));
     std::memcpy(q->h_up.p, segs.data(), bytes);
-    HIPCHK(hipMemcpyAsync(q->segs.p, q->h_up.p, bytes, hipMemcpyHostToDevice, q->ctx->stream));
+    HIPCHK(hipMemcpyAsync(q->segs.p, q->h_up.p, bytes, hipMemcpyHostToDevice, stream ? stream : q->ctx->stream));
     return SH_OK;
 }
 
@@ -556,20 +592,31 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
     RCHK(q->first_bits.reserve((size_t)n_words * 4, false));
     RCHK(q->counters.reserve(64 + (size_t)n_units * 4, false));
     uint32_t* unit_rows = (uint32_t*)(q->counters.as<char>() + 64);  // written by every unit's workgroup
-    HIPCHK(hipMemsetAsync(q->first_bits.p, 0, (size_t)n_words * 4, s));
-    RCHK(upload_segments(q, segs));
+    // a packed split (kPackIdxBits of event index per record) serves segments up to 2^22 events
+    bool long_seg = false;
+    for (auto& sg : segs) long_seg |= sg.hi - sg.lo > (int64_t)kPackIdxMask + 1;
+    if (own && q->ms_ready && q->rec_packed && long_seg) q->ms_ready = false;
+    // a two-stream push whose split is already queued: the bitmap fill, the segment list and the
+    // segment offsets need only the scanned counts, so they run on the side stream beside k_ms_scatter
+    // and the fold waits for them
+    const bool side = q->side_push && own && q->ms_ready;
+    if (!side) q->side_push = false;  // (the split re-run keeps the one stream, compaction included)
+    hipStream_t s2 = side ? q->ctx->side_stream : s;
+    if (side) HIPCHK(hipStreamWaitEvent(s2, q->ev_ms_off, 0));
+    HIPCHK(hipMemsetAsync(q->first_bits.p, 0, (size_t)n_words * 4, s2));
+    RCHK(upload_segments(q, segs, s2));
     const Segment* dsegs = q->segs.as<Segment>();
     SH_TRACE("run_closed nseg=%d closed_hi=%lld row_cap=%lld own=%d P=%d NL=%d ms_ready=%d", nseg, (long long)closed_hi,
              (long long)row_cap, (int)own, q->P, q->NL, (int)q->ms_ready);
     if (own) {
-        // a packed split (kPackIdxBits of event index per record) serves segments up to 2^22 events
-        bool long_seg = false;
-        for (auto& sg : segs) long_seg |= sg.hi - sg.lo > (int64_t)kPackIdxMask + 1;
-        if (q->ms_ready && q->rec_packed && long_seg) q->ms_ready = false;
         if (!q->ms_ready) RCHK(run_multisplit(q, closed_hi, b, false, long_seg));
         RCHK(q->seg_off.reserve((size_t)(nseg + 1) * q->P * 8, false));
-        launch_seg_offsets(s, dsegs, nseg, q->n_pend, q->pend_pos.as<u32>(), pos_src(q, b), q->P,
+        launch_seg_offsets(s2, dsegs, nseg, q->n_pend, q->pend_pos.as<u32>(), pos_src(q, b), q->P,
                            q->ms_counts.as<u32>(), q->ms_map, q->seg_off.as<int64_t>());
+    }
+    if (side) {
+        HIPCHK(hipEventRecord(q->ev_seg, s2));
+        HIPCHK(hipStreamWaitEvent(s, q->ev_seg, 0));
     }
     // (the record buffers' addresses only after run_multisplit: it may have grown them)
     const u32* rec_pos = q->rec_pos.as<u32>();
@@ -742,6 +789,7 @@ static void reset_call_output(sh_query* q) {
     q->flush_window.clear();
     q->dev_out = sh_out{};
     q->ms_ready = false;
+    q->side_push = false;
     q->tail.active = false;
 }
 
@@ -1259,6 +1307,7 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
     int64_t N = b->n;
     const bool cv0 = q->clock_valid;
     const int64_t clock0 = q->clock, seq0 = q->seq;
+    bool swap_spare = false;  // the open window's events were compacted into the spare pending set
     if (N < 0) return sh_fail(SH_ERR_INVALID, "negative batch size");
     if (N > 0 && (!b->ts)) return sh_fail(SH_ERR_INVALID, "batch without timestamps");
     if (q->n_pend + N >= (int64_t)0xFFFFFFF0ll) return sh_fail(SH_ERR_INVALID, "push larger than 4G events");
@@ -1309,22 +1358,28 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
         // otherwise (first timeBatch push, lengthBatch, externalTimeBatch, the sharded owner's given
         // windows) the block-aggregate + scan passes run first
         const bool single_pass = !ext && !q->given && wp.pcol1 == 0 && wp.kind == SH_WIN_TIME_BATCH && wp.e0_valid;
+        // the push's info block sits in front of its boundaries in one allocation, so the host gets both
+        // in one copy (each device-to-host copy is a 4-5 us kernel of its own on the push's critical path)
+        int max_bounds = (int)std::min<int64_t>(N + 1, 1 << 22);
+        constexpr size_t kInfoPad = 2 * sizeof(Bound);
+        static_assert(sizeof(PushInfo) <= kInfoPad, "the info block must fit in front of the boundaries");
+        RCHK(q->bounds.reserve(kInfoPad + (size_t)max_bounds * sizeof(Bound), false));
+        PushInfo* const d_info = q->bounds.as<PushInfo>();
+        Bound* const d_bounds = (Bound*)(q->bounds.as<char>() + kInfoPad);
         auto prefix_passes = [&] {
             launch_blockagg(s, b->ts, cs, q->fp, N, b->send_size, q->blk_pass.as<int64_t>(), q->blk_tl.as<int64_t>(),
                             q->blk_first.as<int64_t>(), nblk, ext ? q->blk_xm.as<int64_t>() : nullptr,
                             ext ? q->d.ts_col : -1);
             launch_scan_blocks(s, q->blk_pass.as<int64_t>(), q->blk_tl.as<int64_t>(), q->blk_first.as<int64_t>(), nblk,
-                               b->ts, wp, q->info.as<PushInfo>(), ext ? q->blk_xm.as<int64_t>() : nullptr, cs);
+                               b->ts, wp, d_info, ext ? q->blk_xm.as<int64_t>() : nullptr, cs);
         };
         if (single_pass) {
             RCHK(q->blk_pass.reserve((size_t)(nblk + 1) * 8, false));
-            launch_zero2(s, q->info.p, (int)sizeof(PushInfo), q->blk_pass.as<int64_t>() + nblk, 8);
+            launch_zero2(s, d_info, (int)sizeof(PushInfo), q->blk_pass.as<int64_t>() + nblk, 8);
             HIPCHK(hipGetLastError());
         } else {
             prefix_passes();
         }
-        int max_bounds = (int)std::min<int64_t>(N + 1, 1 << 22);
-        RCHK(q->bounds.reserve((size_t)max_bounds * sizeof(Bound), false));
         q->direct_pos = want_direct_pos(q);
         if (!q->direct_pos) RCHK(q->new_pos.reserve((size_t)N * 4, false));
         u32* slot_col = q->direct_pos ? nullptr : q->new_pos.as<u32>();
@@ -1333,8 +1388,13 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
         const bool early_split = (q->P > 1 || q->partitioned) && N >= (1 << 18) && !q->d.stream_current;
         const TileMap ms_map = make_tile_map(q->n_pend, q->n_pend + N);
         if (early_split) RCHK(reserve_ms_counts(q, ms_map));
+        // the two-stream layout for this push: the small kernels that do not depend on
+        // their predecessor leave the main stream. Queries with a having program, pass-through rows, a
+        // sharded owner's given windows and externalTimeBatch timeouts (several run_closed calls per
+        // push) keep the one stream.
+        q->side_push = early_split && q->tune.side_stream && !q->hv.on && q->ap.n != 0 && !q->given && q->xt_timeout == 0;
         launch_boundaries(s, b->ts, cs, q->fp, wp, q->blk_pass.as<int64_t>(), q->blk_tl.as<int64_t>(),
-                          q->info.as<PushInfo>(), q->bounds.as<Bound>(), max_bounds, nblk, q->kp, q->kt.dev(),
+                          d_info, d_bounds, max_bounds, nblk, q->kp, q->kt.dev(),
                           slot_col, ext ? q->blk_xm.as<int64_t>() : nullptr,
                           early_split ? q->ms_counts.as<u32>() : nullptr, q->P, ms_map.nblk, ms_map.np_t,
                           single_pass, q->blk_tl.as<int64_t>());
@@ -1346,9 +1406,10 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
         // otherwise read the rest after the split queued behind this copy, the host waiting for it)
         constexpr int kFirstBounds = 256;
         const int nb0 = (int)std::min<int64_t>(max_bounds, std::max<int64_t>(kFirstBounds, q->last_nb + q->last_nb / 4 + 64));
-        RCHK(q->h_bounds.reserve((size_t)nb0 * sizeof(Bound)));
-        HIPCHK(hipMemcpyAsync(q->h_info, q->info.p, sizeof(PushInfo), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(q->h_bounds.p, q->bounds.p, (size_t)nb0 * sizeof(Bound), hipMemcpyDeviceToHost, s));
+        const size_t first_bytes = kInfoPad + (size_t)nb0 * sizeof(Bound);
+        RCHK(q->h_bounds.reserve(first_bytes));
+        const Bound* const h_bounds = (const Bound*)(q->h_bounds.as<char>() + kInfoPad);
+        HIPCHK(hipMemcpyAsync(q->h_bounds.p, q->bounds.p, first_bytes, hipMemcpyDeviceToHost, s));
         if (q->band_spec) {
             // (a speculatively placed band: its overflow word comes back with the push info)
             RCHK(q->h_spec.reserve(16));
@@ -1356,6 +1417,15 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
         }
         HIPCHK(hipEventRecord(q->ev_mid, s));
         SH_TMARK(1);
+        if (q->side_push && ms_map.np_t > 0) {
+            // the queued events' tiles are counted beside k_boundaries, which writes the rows from np_t on
+            // (queued behind k_boundaries' launch: the host's launch time is on an idle GPU's critical path)
+            hipStream_t ss = q->ctx->side_stream;
+            HIPCHK(hipStreamWaitEvent(ss, q->ev_push0, 0));
+            launch_ms_count(ss, ms_map, ms_map.np_t, q->n_pend, q->pend_pos.as<u32>(), pos_src(q, b), q->P,
+                            q->ms_counts.as<u32>());
+            HIPCHK(hipEventRecord(q->ev_cnt, ss));
+        }
         if (early_split) RCHK(run_multisplit(q, q->n_pend + N, b, true));
         SH_TRACE("push N=%lld n_pend=%lld: boundaries queued", (long long)N, (long long)q->n_pend);
         SH_TMARK(2);
@@ -1365,6 +1435,8 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
         }
         HIPCHK(sh_wait_event(q->ev_mid));
         SH_TMARK(3);
+        // (h_info keeps the push's info for later readers: sc_rows)
+        *q->h_info = *q->h_bounds.as<PushInfo>();
         PushInfo info = *q->h_info;
         SH_TRACE("push info: pass=%lld bounds=%d", (long long)info.total_pass, info.n_bounds);
         if (q->band_spec && q->h_spec.as<uint32_t>()[2] == 3) {
@@ -1377,12 +1449,12 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
             SH_TRACE("push: unsorted timestamps, window assignment redone with the prefix passes");
             prefix_passes();
             launch_boundaries(s, b->ts, cs, q->fp, wp, q->blk_pass.as<int64_t>(), q->blk_tl.as<int64_t>(),
-                              q->info.as<PushInfo>(), q->bounds.as<Bound>(), max_bounds, nblk, q->kp, q->kt.dev(),
+                              d_info, d_bounds, max_bounds, nblk, q->kp, q->kt.dev(),
                               slot_col, nullptr);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(q->h_info, q->info.p, sizeof(PushInfo), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(q->h_bounds.p, q->bounds.p, (size_t)nb0 * sizeof(Bound), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(q->h_bounds.p, q->bounds.p, first_bytes, hipMemcpyDeviceToHost, s));
             HIPCHK(sh_wait_stream(s));
+            *q->h_info = *q->h_bounds.as<PushInfo>();
             info = *q->h_info;
         }
         if (info.n_bounds > max_bounds) return sh_fail(SH_ERR_INVALID, "more than 4M windows closed in one push");
@@ -1395,9 +1467,9 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
         q->last_nb = std::min<int64_t>(info.n_bounds, 1 << 16);
         if (info.n_bounds) {
             if (info.n_bounds <= nb0) {
-                std::memcpy(bounds.data(), q->h_bounds.p, info.n_bounds * sizeof(Bound));
+                std::memcpy(bounds.data(), h_bounds, info.n_bounds * sizeof(Bound));
             } else {
-                HIPCHK(hipMemcpyAsync(bounds.data(), q->bounds.p, info.n_bounds * sizeof(Bound), hipMemcpyDeviceToHost, s));
+                HIPCHK(hipMemcpyAsync(bounds.data(), d_bounds, info.n_bounds * sizeof(Bound), hipMemcpyDeviceToHost, s));
                 HIPCHK(hipStreamSynchronize(s));
             }
             std::sort(bounds.begin(), bounds.end(), [](const Bound& a, const Bound& c) { return a.idx < c.idx; });
@@ -1496,6 +1568,23 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
             if (M > n_old || (q->d.expired_on && !bounds.empty() && n_old > 0))
                 RCHK(sc_rows(q, b, bounds, n_old, M, cv0, clock0, seq0, host_out));
             RCHK(pending_to_front(q, M - new_pend, new_pend));
+        } else if (q->side_push && dst_base == 0) {
+            // a window closed: the open window's events start a fresh pending set. The fold, the emission
+            // and the split still read the old set, so the new one is written into the spare buffers, on
+            // the side stream beside them (its inputs — the slots and tile prefixes k_boundaries left —
+            // are on the device since the host read the boundaries); the sets change places below
+            RCHK(grow_spare(q, new_pend));
+            hipStream_t ss = q->ctx->side_stream;
+            // (beside the fold, whose workgroups leave room on every CU, not beside the bandwidth-bound
+            // k_ms_scatter: there the two slowed each other down, 48 us + 10 us against 24 us alone)
+            HIPCHK(hipStreamWaitEvent(ss, q->ev_agg0, 0));
+            launch_compact_pending(ss, b->ts, cs, pos_src(q, b), q->ap, e_lo, N, pcb_lo, 0, q->blk_pass.as<int64_t>(),
+                                   q->sp_pos.as<u32>(), q->sp_ts.as<int64_t>(), q->sp_vals.as<u64>(), q->sp_cap, nullptr,
+                                   q->sp_gidx.as<u64>(), q->seq);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(q->ev_cmp, ss));
+            HIPCHK(hipStreamWaitEvent(s, q->ev_cmp, 0));  // (ev_push1 and the final wait cover it)
+            swap_spare = true;
         } else {
             RCHK(grow_pending(q, new_pend, dst_base));
             launch_compact_pending(s, b->ts, cs, pos_src(q, b), q->ap, e_lo, N, pcb_lo, dst_base,
@@ -1516,6 +1605,9 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
     HIPCHK(sh_wait_stream(s));
     SH_TMARK(5);
     SH_TRACE("push done");
+    // (the main stream waited for the side stream's last event: both are idle, nothing reads the old set)
+    if (swap_spare) swap_pending(q);
+    q->side_push = false;
     RCHK(q->kt.check_result(q->h_tail.as<uint32_t>()));
     RCHK(closed_finish(q, host_out));
     float ms = 0;
@@ -1857,6 +1949,7 @@ extern "C" int sh_query_destroy(sh_query* q) {
     (void)small_verify(q, true);  // the queued appends read the ring and pending buffers freed below
     (void)hipStreamSynchronize(q->ctx->stream);
     (void)hipStreamSynchronize(q->ctx->copy_stream);
+    (void)hipStreamSynchronize(q->ctx->side_stream);
     {
         // staging slots were allocated outside stream order (sh_ingest.cpp)
         StreamScope none(nullptr);
@@ -1875,7 +1968,8 @@ extern "C" int sh_query_destroy(sh_query* q) {
     if (q->h_info) (void)hipHostFree(q->h_info);
     if (q->small_res) (void)hipHostFree(q->small_res);
     if (q->zc_ring) (void)hipHostFree(q->zc_ring);
-    hipEvent_t evs[] = {q->ev_push0, q->ev_push1, q->ev_agg0, q->ev_agg1, q->ev_mid, q->ev_srt0, q->ev_srt1};
+    hipEvent_t evs[] = {q->ev_push0, q->ev_push1, q->ev_agg0, q->ev_agg1, q->ev_mid, q->ev_srt0, q->ev_srt1,
+                        q->ev_cnt, q->ev_ms_off, q->ev_seg, q->ev_cmp};
     for (auto e : evs) if (e) (void)hipEventDestroy(e);
     delete q;
     return SH_OK;
@@ -1909,10 +2003,15 @@ int run_multisplit(sh_query* q, int64_t hi, const sh_batch* b, bool counted, boo
     RCHK(q->rec_vals.reserve(std::max(1, q->ap.n_vcols) * cap * 8, false));
     const PosSrc np = pos_src(q, b);
     // the queued events' tiles (every tile when k_boundaries did not count); also zeroes the total slot
-    launch_ms_count(s, m, counted ? m.np_t : m.nblk, q->n_pend, q->pend_pos.as<u32>(), np, P, q->ms_counts.as<u32>());
+    // (a two-stream push counted the queued events' tiles on the side stream, beside k_boundaries)
+    const bool side = counted && q->side_push;
+    if (!side) launch_ms_count(s, m, counted ? m.np_t : m.nblk, q->n_pend, q->pend_pos.as<u32>(), np, P, q->ms_counts.as<u32>());
+    else if (m.np_t > 0) HIPCHK(hipStreamWaitEvent(s, q->ev_cnt, 0));
     // counts (u32: a push holds fewer than 2^32 events) are laid out [p][blk]; one exclusive scan
     // gives every (partition, block) its offset, and partition p starts at offset[p * nblk]
     launch_ms_offsets(s, q->ms_counts.as<u32>(), m.nblk, P, q->ms_tmp.as<int64_t>());
+    // the scanned counts are all the segment offsets wait for (k_seg_offsets reads no record)
+    if (side) HIPCHK(hipEventRecord(q->ev_ms_off, s));
     launch_ms_scatter(s, m, q->n_pend, q->pend_pos.as<u32>(), q->pend_vals.as<u64>(), q->pend_cap, np, cs, q->ap, P,
                       q->logP, q->ms_counts.as<u32>(), pack ? nullptr : q->rec_pos.as<u32>(), q->rec_idx.as<u32>(),
                       q->rec_vals.as<u64>(), cap, pack);
