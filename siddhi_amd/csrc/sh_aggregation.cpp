@@ -1191,7 +1191,7 @@ static int group_fold(sh_aggregation* a, const int64_t* bucket, const int64_t* k
         RCHK(a->wk.decode(s, key, n, a->g_dk.as<int64_t>()));
         for (int x = ng - 1; x >= 0; x--) RCHK(pass(a->g_dk.as<int64_t>() + (size_t)x * n, 1ull << 63));
     } else {
-        RCHK(pass(key, 0));
+        RCHK(pass(key, 1ull << 63));  // (signed too: a negative int / long key comes before the positive ones)
     }
     RCHK(pass(a->g_bucket.as<int64_t>(), 0));
     if (c != 2) HIPCHK(hipMemcpyAsync(idx[2], idx[c], n * 4, hipMemcpyDeviceToDevice, s));

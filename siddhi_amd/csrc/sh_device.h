@@ -317,6 +317,14 @@ __device__ __forceinline__ void unpack_key(const KeyPlan& kp, u64 key, i64* out,
     }
 }
 
+// A two-column group key packed again from the components sh_out reports (unpack_part). Bit g of fmask: the
+// component is a float, reported as the bits of its value widened to double — its low 32 bits say nothing.
+__device__ __forceinline__ u64 repack_key2(i64 a, i64 b, int fmask) {
+    const u32 x = (fmask & 1) ? __float_as_uint((float)__longlong_as_double(a)) : (u32)a;
+    const u32 y = (fmask & 2) ? __float_as_uint((float)__longlong_as_double(b)) : (u32)b;
+    return ((u64)x << 32) | (u64)y;
+}
+
 __device__ __forceinline__ u64 mix64(u64 z) {
     z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
     z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
@@ -360,9 +368,17 @@ __device__ __forceinline__ u32 dense_slot(const KeyTable& kt, u64 key) {
     return s;
 }
 
+// The slot of a key equal to the EMPTY sentinel: mask + 1, behind the table. Handing it out sets the
+// table's second control word (KeyTableHost::reserved_used), so a consumer that packs slot values can
+// count size + 1 of them only when that slot is live (sh_stream_current.cpp sc_rows).
+__device__ __forceinline__ u32 reserved_slot(const KeyTable& kt) {
+    atomicOr(&kt.n_keys[1], 1u);  // (as the insert counter beside it: read in the small-push kernel's report too)
+    return kt.mask + 1;
+}
+
 __device__ __forceinline__ u32 key_slot(const KeyTable& kt, u64 key) {
     if (kt.dense) return dense_slot(kt, key);
-    if (key == kEmptyKey) return kt.mask + 1;
+    if (key == kEmptyKey) return reserved_slot(kt);
     u32 h = key_home(kt, key);
     for (u32 probe = 0; probe <= kt.mask; probe++)
         if (probe_step(kt, key, kt.keys[h], h)) return h;
@@ -384,7 +400,7 @@ __device__ __forceinline__ void key_slots(const KeyTable& kt, const u64* key, co
 #pragma unroll
     for (int i = 0; i < K; i++) {
         done[i] = !valid[i] || key[i] == kEmptyKey;
-        if (valid[i] && key[i] == kEmptyKey) out[i] = kt.mask + 1;
+        if (valid[i] && key[i] == kEmptyKey) out[i] = reserved_slot(kt);
         h[i] = key_home(kt, key[i]);
     }
     for (u32 probe = 0; probe <= kt.mask; probe++) {

@@ -200,7 +200,7 @@ int xout_finish(sh_query* q, bool host_out, const sh_out** out) {
             RCHK(q->x_trow.reserve((size_t)tab_total * 4, false));
             RCHK(q->x_tkey.reserve((size_t)tab_total * 8, false));
             HIPCHK(hipMemsetAsync(q->x_trow.p, 0xff, (size_t)tab_total * 4, s));
-            launch_x_merge(s, d_items, d_cum_c, d_cum_p, ni, cum_c[ni], cum_p[ni], q->xs_keys.as<int64_t>(), S, nk,
+            launch_x_merge(s, d_items, d_cum_c, d_cum_p, ni, cum_c[ni], cum_p[ni], q->xs_keys.as<int64_t>(), S, nk, key_float_mask(q->kp),
                            q->x_trow.as<uint32_t>(), q->x_tkey.as<u64>(), q->x_match.as<int>(),
                            q->x_keep.as<uint32_t>(), q->x_matched.as<uint32_t>());
             HIPCHK(hipGetLastError());

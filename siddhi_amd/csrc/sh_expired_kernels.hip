@@ -22,10 +22,10 @@ namespace shd {
 
 constexpr u32 kXEmpty = 0xFFFFFFFFu;
 
-__device__ __forceinline__ u64 x_packed_key(const i64* keys, i64 stride, int nk, i64 r) {
+__device__ __forceinline__ u64 x_packed_key(const i64* keys, i64 stride, int nk, int fmask, i64 r) {
     if (nk == 0) return 0;
     if (nk == 1) return (u64)keys[r];
-    return ((u64)(u32)keys[r] << 32) | (u64)(u32)keys[stride + r];
+    return repack_key2(keys[r], keys[stride + r], fmask);
 }
 
 // largest i with cum[i] <= g (cum[0] = 0, non-decreasing)
@@ -41,13 +41,13 @@ __device__ __forceinline__ int x_find(const i64* cum, int n, i64 g) {
 // Current rows of the merged flushes into their flush's open-addressing table (keys within one
 // flush are distinct, so an insert only claims the first free slot).
 __global__ __launch_bounds__(kBlock) void k_x_insert(const XItem* items, const i64* cum, int n_items, i64 total,
-                                                     const i64* s_keys, i64 S, int nk, u32* trow, u64* tkey) {
+                                                     const i64* s_keys, i64 S, int nk, int fmask, u32* trow, u64* tkey) {
     const i64 g = (i64)blockIdx.x * kBlock + threadIdx.x;
     if (g >= total) return;
     const int i = x_find(cum, n_items + 1, g);
     const XItem it = items[i];
     const i64 r = it.c_lo + (g - cum[i]);
-    const u64 key = x_packed_key(s_keys, S, nk, r);
+    const u64 key = x_packed_key(s_keys, S, nk, fmask, r);
     if (it.pad) {  // (a dense id below the table size: its own slot, distinct within the flush)
         if (key < (u64)it.tab_size) trow[it.tab_off + (i64)key] = (u32)r;
         return;
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(kBlock) void k_x_insert(const XItem* items, const i
 // Expired rows of the merged flushes look up their key among the flush's current rows: match[r] =
 // that current row (or -1); the matched current row is not emitted a second time.
 __global__ __launch_bounds__(kBlock) void k_x_probe(const XItem* items, const i64* cum, int n_items, i64 total,
-                                                    const i64* s_keys, i64 S, int nk, const u32* trow, const u64* tkey,
+                                                    const i64* s_keys, i64 S, int nk, int fmask, const u32* trow, const u64* tkey,
                                                     int* match, u32* keep, u32* item_matched) {
     const i64 g = (i64)blockIdx.x * kBlock + threadIdx.x;
     const bool valid = g < total;
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(kBlock) void k_x_probe(const XItem* items, const i6
         i = x_find(cum, n_items + 1, g);
         const XItem it = items[i];
         const i64 r = it.p_lo + (g - cum[i]);
-        const u64 key = x_packed_key(s_keys, S, nk, r);
+        const u64 key = x_packed_key(s_keys, S, nk, fmask, r);
         int m = -1;
         if (it.pad) {  // (direct table: the id is the slot)
             const u32 t = key < (u64)it.tab_size ? trow[it.tab_off + (i64)key] : kXEmpty;
@@ -182,14 +182,14 @@ __global__ __launch_bounds__(kBlock) void k_x_scatter(const XItem* items, const 
 }
 
 void launch_x_merge(hipStream_t s, const XItem* items, const i64* cum_c, const i64* cum_p, int n_items, i64 tot_c,
-                    i64 tot_p, const i64* s_keys, i64 S, int nk, u32* trow, u64* tkey, int* match, u32* keep,
+                    i64 tot_p, const i64* s_keys, i64 S, int nk, int fmask, u32* trow, u64* tkey, int* match, u32* keep,
                     u32* item_matched) {
     if (tot_c > 0)
         hipLaunchKernelGGL(k_x_insert, dim3((unsigned)((tot_c + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, items, cum_c,
-                           n_items, tot_c, s_keys, S, nk, trow, tkey);
+                           n_items, tot_c, s_keys, S, nk, fmask, trow, tkey);
     if (tot_p > 0)
         hipLaunchKernelGGL(k_x_probe, dim3((unsigned)((tot_p + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, items, cum_p,
-                           n_items, tot_p, s_keys, S, nk, trow, tkey, match, keep, item_matched);
+                           n_items, tot_p, s_keys, S, nk, fmask, trow, tkey, match, keep, item_matched);
 }
 
 void launch_x_scatter(hipStream_t s, const XItem* items, const i64* cum, int n_items, i64 total, const i64* s_ts,

@@ -97,6 +97,12 @@ struct KeyPlan {
     i64 div[kKeyParts];  // > 0: the component is (u32)((value + add) / div) (aggregation time buckets)
     i64 add[kKeyParts];  // (the aggregation time zone's offset for hour / day buckets)
 };
+// bit g: component g of a two-column key is a float (repack_key2: rows report it widened to double)
+inline int key_float_mask(const KeyPlan& kp) {
+    int m = 0;
+    for (int g = 0; g < kp.n && kp.n == 2; g++) m |= kp.type[g] == SH_T_FLOAT ? 1 << g : 0;
+    return m;
+}
 
 // Hash table (key -> position = group slot). positions [0, mask] plus the reserved mask+1
 // for a key equal to the EMPTY sentinel.
@@ -379,7 +385,7 @@ struct XOut {
     const i64* s_order;    // ... and the source rows' order
 };
 void launch_x_merge(hipStream_t s, const XItem* items, const i64* cum_c, const i64* cum_p, int n_items, i64 tot_c,
-                    i64 tot_p, const i64* s_keys, i64 S, int nk, u32* trow, u64* tkey, int* match, u32* keep,
+                    i64 tot_p, const i64* s_keys, i64 S, int nk, int fmask, u32* trow, u64* tkey, int* match, u32* keep,
                     u32* item_matched);
 void launch_x_scatter(hipStream_t s, const XItem* items, const i64* cum, int n_items, i64 total, const i64* s_ts,
                       const i64* s_keys, const u64* s_vals, const unsigned char* s_nulls, const i64* s_rep, i64 S,
@@ -402,7 +408,7 @@ struct RateRows {
 void launch_rate_pos(hipStream_t s, i64 n_src, i64 n_carry, int mode, i64 N, i64 seq0, const i64* flush_off, int nf,
                      u32* flag, int* eflush, u32* src);
 void launch_rate_clear(hipStream_t s, i64 n, u32* src, u32* flag);
-void launch_rate_pack(hipStream_t s, i64 n, const i64* keys, i64 stride, int nk, u64* skey, u32* idx);
+void launch_rate_pack(hipStream_t s, i64 n, const i64* keys, i64 stride, int nk, int fmask, u64* skey, u32* idx);
 void launch_rate_segments(hipStream_t s, i64 n, const u64* skey, const u32* idx, i64 N, int with_win, u32* hd, u32* pos,
                           u32* starts, i64* tmp);
 void launch_rate_first(hipStream_t s, i64 n, const u32* hd, const u32* pos, const u32* starts, const u64* skey,

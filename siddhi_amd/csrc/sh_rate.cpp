@@ -105,11 +105,14 @@ static int grow_ftime_table(sh_query* q, int64_t need) {
     while (cap < 2 * need) cap <<= 1;
     if (cap > ((int64_t)1 << 31)) return sh_fail(SH_ERR_UNSUPPORTED, "output rate: too many group keys");
     if (cap <= r.ft_cap) return SH_OK;
-    RCHK(r.ftk2.reserve((size_t)cap * 8, false));
-    RCHK(r.ftt2.reserve((size_t)cap * 8, false));
-    // kEmptyKey (0x8000000000000001) in every slot
-    std::vector<uint64_t> empty((size_t)cap, kEmptyKey);
-    HIPCHK(hipMemcpyAsync(r.ftk2.p, empty.data(), (size_t)cap * 8, hipMemcpyHostToDevice, s));
+    // cap slots and, behind them, the entry of the key equal to kEmptyKey (k_rate_ftime_walk)
+    const size_t bytes = ((size_t)cap + 1) * 8;
+    RCHK(r.ftk2.reserve(bytes, false));
+    RCHK(r.ftt2.reserve(bytes, false));
+    // kEmptyKey (0x8000000000000001) in every slot, time 0
+    std::vector<uint64_t> empty((size_t)cap + 1, kEmptyKey);
+    HIPCHK(hipMemcpyAsync(r.ftk2.p, empty.data(), bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(r.ftt2.p, 0, bytes, s));
     if (r.ft_cap > 0)
         launch_rate_ftime_rehash(s, r.ft_cap, r.ftk.as<u64>(), r.ftt.as<i64>(), r.ftk2.as<u64>(), r.ftt2.as<i64>(),
                                  (u32)(cap - 1));
@@ -339,7 +342,7 @@ int rate_apply(sh_query* q, const sh_out* in, bool flush_dev, bool host_out, con
         RCHK(r.starts.reserve((size_t)(m + 1) * 4, false));
         RCHK(r.tmp.reserve((size_t)((m + 1 + kTile - 1) / kTile + 16) * 8, false));
         if (r.pkey) launch_ratep_pkey(s, m, src.keys, plane_out_part(q), r.skey.as<u64>(), r.idx.as<u32>());
-        else launch_rate_pack(s, m, src.keys, sstride, nk, r.skey.as<u64>(), r.idx.as<u32>());
+        else launch_rate_pack(s, m, src.keys, sstride, nk, nk == 2 ? key_float_mask(q->kp) : 0, r.skey.as<u64>(), r.idx.as<u32>());
         size_t tb = 0;
         if (sort_u64_pairs(nullptr, &tb, nullptr, nullptr, nullptr, nullptr, m, s))
             return sh_fail(SH_ERR_DEVICE, "output rate: sort sizing");
@@ -374,7 +377,7 @@ int rate_apply(sh_query* q, const sh_out* in, bool flush_dev, bool host_out, con
             RCHK(r.starts.reserve((size_t)(m + 1) * 4, false));
             RCHK(r.tmp.reserve((size_t)((m + 1 + kTile - 1) / kTile + 16) * 8, false));
             if (r.pkey) launch_ratep_pkey(s, m, src.keys, plane_out_part(q), r.skey.as<u64>(), r.idx.as<u32>());
-            else launch_rate_pack(s, m, src.keys, sstride, nk, r.skey.as<u64>(), r.idx.as<u32>());
+            else launch_rate_pack(s, m, src.keys, sstride, nk, nk == 2 ? key_float_mask(q->kp) : 0, r.skey.as<u64>(), r.idx.as<u32>());
             size_t tb = 0;
             if (sort_u64_pairs(nullptr, &tb, nullptr, nullptr, nullptr, nullptr, m, s))
                 return sh_fail(SH_ERR_DEVICE, "output rate: sort sizing");

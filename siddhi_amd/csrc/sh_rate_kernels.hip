@@ -23,10 +23,10 @@ __device__ __forceinline__ int rate_flush_of(const i64* off, int nf, i64 r) {  /
     return lo;
 }
 
-__device__ __forceinline__ u64 rate_key(const i64* keys, i64 stride, int nk, i64 r) {
+__device__ __forceinline__ u64 rate_key(const i64* keys, i64 stride, int nk, int fmask, i64 r) {
     if (nk == 0) return 0;
     if (nk == 1) return (u64)keys[r];
-    return ((u64)(u32)keys[r] << 32) | (u64)(u32)keys[stride + r];
+    return repack_key2(keys[r], keys[stride + r], fmask);
 }
 
 // Positional limiters (no group key), one thread per source row; flag[n_src] = 0 closes the scan.
@@ -57,11 +57,11 @@ __global__ __launch_bounds__(kBlock) void k_rate_pos(i64 n_src, i64 n_carry, int
 }
 
 // ---- group-by limiters over the rows sorted (stably) by packed key --------------------------------
-__global__ __launch_bounds__(kBlock) void k_rate_pack(i64 n, const i64* __restrict__ keys, i64 stride, int nk,
+__global__ __launch_bounds__(kBlock) void k_rate_pack(i64 n, const i64* __restrict__ keys, i64 stride, int nk, int fmask,
                                                      u64* skey, u32* idx) {
     const i64 i = (i64)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    skey[i] = rate_key(keys, stride, nk, i);
+    skey[i] = rate_key(keys, stride, nk, fmask, i);
     idx[i] = (u32)i;
 }
 
@@ -232,9 +232,9 @@ void launch_rate_clear(hipStream_t s, i64 n, u32* src, u32* flag) {
     hipLaunchKernelGGL(k_rate_clear, dim3(grid_of(n + 1)), dim3(kBlock), 0, s, n, src, flag);
 }
 
-void launch_rate_pack(hipStream_t s, i64 n, const i64* keys, i64 stride, int nk, u64* skey, u32* idx) {
+void launch_rate_pack(hipStream_t s, i64 n, const i64* keys, i64 stride, int nk, int fmask, u64* skey, u32* idx) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_rate_pack, dim3(grid_of(n)), dim3(kBlock), 0, s, n, keys, stride, nk, skey, idx);
+    hipLaunchKernelGGL(k_rate_pack, dim3(grid_of(n)), dim3(kBlock), 0, s, n, keys, stride, nk, fmask, skey, idx);
 }
 
 void launch_rate_segments(hipStream_t s, i64 n, const u64* skey, const u32* idx, i64 N, int with_win, u32* hd, u32* pos,
@@ -301,6 +301,8 @@ void launch_rate_ftime_rows(hipStream_t s, i64 n, const i64* foff, int nf, const
 // (groupByOutputTime); a row is sent when its key has none or that time + t <= the chunk's clock. One
 // thread per key segment of the call (rows of one key in stream order); the key -> time table keeps
 // the keys of earlier calls (tk == kEmptyKey: free; a thread only ever claims or reads its own key's slot).
+// A key equal to that free mark has the entry behind the table, tmask + 1, to itself: its tk word is the
+// free mark until the key's first row and 0 from then on.
 __global__ __launch_bounds__(kBlock) void k_rate_ftime_walk(i64 n, const u32* __restrict__ hd, const u32* __restrict__ pos,
                                                            const u32* __restrict__ starts, const u64* __restrict__ skey,
                                                            const u32* __restrict__ idx, const i64* __restrict__ foff,
@@ -313,15 +315,21 @@ __global__ __launch_bounds__(kBlock) void k_rate_ftime_walk(i64 n, const u32* __
     const u64 key = skey[i];
     u32 h = (u32)mix64(key) & tmask;
     bool has = true;
-    for (;;) {
-        const u64 k0 = tk[h];
-        if (k0 == key) break;
-        if (k0 == kEmptyKey) {
-            const u64 old = atomicCAS(&tk[h], kEmptyKey, key);
-            if (old == kEmptyKey) { has = false; atomicAdd(n_new, 1u); break; }
-            if (old == key) break;
+    if (key == kEmptyKey) {
+        h = tmask + 1;
+        has = tk[h] != kEmptyKey;
+        tk[h] = 0;
+    } else {
+        for (;;) {
+            const u64 k0 = tk[h];
+            if (k0 == key) break;
+            if (k0 == kEmptyKey) {
+                const u64 old = atomicCAS(&tk[h], kEmptyKey, key);
+                if (old == kEmptyKey) { has = false; atomicAdd(n_new, 1u); break; }
+                if (old == key) break;
+            }
+            h = (h + 1) & tmask;
         }
-        h = (h + 1) & tmask;
     }
     i64 last = has ? tt[h] : 0;
     for (i64 j = i; j < end; j++) {
@@ -336,14 +344,19 @@ __global__ __launch_bounds__(kBlock) void k_rate_ftime_walk(i64 n, const u32* __
     tt[h] = last;
 }
 
+// one thread per entry of the old table and one for the entry behind it (the key equal to the free mark)
 __global__ __launch_bounds__(kBlock) void k_rate_ftime_rehash(i64 old_cap, const u64* __restrict__ otk,
                                                              const i64* __restrict__ ott, u64* tk, i64* tt, u32 tmask) {
     const i64 i = (i64)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= old_cap) return;
+    if (i > old_cap) return;
     const u64 key = otk[i];
     if (key == kEmptyKey) return;
-    u32 h = (u32)mix64(key) & tmask;
-    while (atomicCAS(&tk[h], kEmptyKey, key) != kEmptyKey) h = (h + 1) & tmask;
+    u32 h = tmask + 1;
+    if (i == old_cap) tk[h] = key;
+    else {
+        h = (u32)mix64(key) & tmask;
+        while (atomicCAS(&tk[h], kEmptyKey, key) != kEmptyKey) h = (h + 1) & tmask;
+    }
     tt[h] = ott[i];
 }
 
@@ -357,7 +370,7 @@ void launch_rate_ftime_walk(hipStream_t s, i64 n, const u32* hd, const u32* pos,
 
 void launch_rate_ftime_rehash(hipStream_t s, i64 old_cap, const u64* otk, const i64* ott, u64* tk, i64* tt, u32 tmask) {
     if (old_cap <= 0) return;
-    hipLaunchKernelGGL(k_rate_ftime_rehash, dim3(grid_of(old_cap)), dim3(kBlock), 0, s, old_cap, otk, ott, tk, tt, tmask);
+    hipLaunchKernelGGL(k_rate_ftime_rehash, dim3(grid_of(old_cap + 1)), dim3(kBlock), 0, s, old_cap, otk, ott, tk, tt, tmask);
 }
 
 // ---- one limiter per partition instance (PartitionRuntimeImpl clones the query, so each partition

@@ -418,6 +418,7 @@ int KeyTableHost::init_size(size_t ts) {
     lk = 0;
     size_ = ts;
     n_keys = 0;
+    reserved_used = false;
     int rc = keys.reserve(ts * 8, false);
     if (rc) return rc;
     rc = ctrl.reserve(64, false);
@@ -455,6 +456,7 @@ int KeyTableHost::check_async(hipStream_t s, uint32_t* pinned4) {
 
 int KeyTableHost::check_result(const uint32_t* c) {
     n_keys = c[0];
+    reserved_used |= c[1] != 0;
     if (c[2] == 2) return sh_fail(SH_ERR_INVALID, "dictionary id outside [0, key_capacity): raise key_capacity");
     if (c[2] == 3) return sh_fail(SH_ERR_DEVICE, "aggregation time bucket outside the root key band");
     if (c[2]) return sh_fail(SH_ERR_INVALID, "group key table full: raise key_capacity");

@@ -128,6 +128,8 @@ struct KeyTableHost {
     PinnedBuf h_ctrl;  // landing area of check()
     size_t size_ = 0;
     int64_t n_keys = 0;  // keys inserted so far (read back by check)
+    // a lookup handed out the reserved slot mask + 1 (the key equal to EMPTY; read back by check, sticky)
+    bool reserved_used = false;
     bool dense = false;  // dictionary ids: slot = (id - dadd) / dmul, no hashing
     uint32_t dmul = 1, dadd = 0;
     // band mode (KeyTable::lk): rows of 2^lk slots for the time buckets [b0, b0 + rows)

@@ -31,7 +31,7 @@ using namespace shd;
 
 namespace {
 
-constexpr uint32_t kVersion = 7;  // 5: band key mode, sharded aggregation sections; 6: timeout / limiter in the fingerprint; 7: replaceTimestampWithBatchEndTime
+constexpr uint32_t kVersion = 8;  // 5: band key mode, sharded aggregation sections; 6: timeout / limiter in the fingerprint; 7: replaceTimestampWithBatchEndTime; 8: the first_time limiter's reserved entry
 
 struct Writer {
     std::vector<uint8_t> b;
@@ -112,6 +112,9 @@ int set_key_count(sh_query* q, int64_t nk) {
     RCHK(h.reserve(16));
     uint32_t* c = h.as<uint32_t>();
     c[0] = (uint32_t)nk; c[1] = c[2] = c[3] = 0;
+    // (a blob does not say whether the restored slots include the reserved one, mask + 1: assume they do)
+    q->kt.reserved_used = !q->kt.dense;
+    c[1] = q->kt.reserved_used ? 1 : 0;
     if (hipMemcpyAsync(q->kt.ctrl.p, c, 16, hipMemcpyHostToDevice, q->ctx->stream) != hipSuccess ||
         hipStreamSynchronize(q->ctx->stream) != hipSuccess)
         return sh_fail(SH_ERR_DEVICE, "restore: key table counter");
@@ -306,8 +309,10 @@ static int rate_snapshot(sh_query* q, Writer& w) {
     w.val<int64_t>(r.ft_last);
     w.val<int64_t>(r.ft_cap);
     w.val<int64_t>(r.ft_keys);
-    RCHK(w.dev(r.ftk.p, (size_t)r.ft_cap * 8, s));
-    RCHK(w.dev(r.ftt.p, (size_t)r.ft_cap * 8, s));
+    // (the table's slots and the entry behind them, grow_ftime_table)
+    const size_t ftb = r.ft_cap ? ((size_t)r.ft_cap + 1) * 8 : 0;
+    RCHK(w.dev(r.ftk.p, ftb, s));
+    RCHK(w.dev(r.ftt.p, ftb, s));
     if (r.part) {  // one limiter per partition: the carried rows' partitions and every partition's state
         const size_t np = (size_t)r.nparts;
         RCHK(w.dev(r.c_part.p, n * 4, s));

@@ -55,7 +55,8 @@ static int reserve_walk(sh_query* q, int64_t M) {
 // This one loop gives what the two earlier ones gave for every table size up to 2^32 (pend_pos is a u32,
 // so larger tables cannot occur). kb is the smallest k >= 1 with 2^k >= n_slots. stream.current passes
 // the table size: its loop `kb < 32 && 2^kb < size` stopped at that same k, which is at most 32 for a
-// size up to 2^32, so its cap never bound and the kb <= 32 test below never fails for it. `having`
+// size up to 2^32, so its cap never bound and the kb <= 32 test below never fails for it (once a key equal to
+// EMPTY holds the reserved slot it passes the table size + 1, as `having` does). `having`
 // passes the table size + 1: its loop `kb < 33 && 2^kb <= size` is this loop literally, and it kept the
 // keys unpacked when kb reached 33 (a table of 2^32 slots), as the test below does.
 static unsigned sort_end_bit(uint64_t n_slots, int64_t n_windows, unsigned* kb_out) {
@@ -378,8 +379,11 @@ int sc_rows(sh_query* q, const sh_batch* b, const std::vector<Bound>& bounds, in
                    gv ? 1 : 0);
     // current rows only: the radix sort reads the slot and window bits alone (C2: 24 of 64); the expired
     // rows' kernels read the keys whole
-    // (the slot count here leaves out the sentinel key's slot, mask + 1, which hv_closed counts)
-    const unsigned end_bit = xs || xt ? 64 : pack_keys(q, M, q->kt.size_, nb);
+    // (the reserved slot mask + 1 takes one more slot bit, which may be one more sort pass: counted only once
+    // a key equal to EMPTY has been looked up: the table's control words say so, read back at the end of
+    // every push and, for this push's own lookups, beside the push info — sh_window.cpp)
+    const bool rsv = q->kt.reserved_used;
+    const unsigned end_bit = xs || xt ? 64 : pack_keys(q, M, (uint64_t)q->kt.size_ + (rsv ? 1 : 0), nb);
     RCHK(sort_runs(q, M, end_bit, "stream.current"));
     // (a program with expired output: the closing windows' runs are walked again with the remove forms, and
     // the expired rows are those of the passing heads — scx_fe — instead of every key of a closing window)

@@ -1410,7 +1410,10 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
         RCHK(q->h_bounds.reserve(first_bytes));
         const Bound* const h_bounds = (const Bound*)(q->h_bounds.as<char>() + kInfoPad);
         HIPCHK(hipMemcpyAsync(q->h_bounds.p, q->bounds.p, first_bytes, hipMemcpyDeviceToHost, s));
-        if (q->band_spec) {
+        // stream.current over a hashed table packs (window, slot) sort keys (sc_rows): whether this push's
+        // lookups handed out the reserved slot, mask + 1, comes back with the push info until it is known
+        const bool rsv_probe = q->d.stream_current && !q->kt.dense && !q->kt.reserved_used;
+        if (q->band_spec || rsv_probe) {
             // (a speculatively placed band: its overflow word comes back with the push info)
             RCHK(q->h_spec.reserve(16));
             RCHK(q->kt.check_async(s, q->h_spec.as<uint32_t>()));
@@ -1439,6 +1442,7 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
         *q->h_info = *q->h_bounds.as<PushInfo>();
         PushInfo info = *q->h_info;
         SH_TRACE("push info: pass=%lld bounds=%d", (long long)info.total_pass, info.n_bounds);
+        if (rsv_probe && q->h_spec.as<uint32_t>()[1]) q->kt.reserved_used = true;
         if (q->band_spec && q->h_spec.as<uint32_t>()[2] == 3) {
             SH_TRACE("push: a bucket outside the speculative key band, retried after a probe");
             return kRetryBand;
