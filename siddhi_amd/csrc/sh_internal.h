@@ -236,7 +236,9 @@ void launch_aggregate(hipStream_t s, const Segment* segs, int nseg, int P, int l
                       AggPlan ap, u64* rows, int RW, u32* unit_rows, u32* first_bits,
                       // multisplit source (P > 1 or long windows; null: the flat kernel reads the batch)
                       const u32* rec_pos, const u32* rec_idx, const u64* rec_vals, i64 rec_cap, const i64* seg_off,
-                      bool pack, EvSrc es, bool dense_rows = false);
+                      bool pack, EvSrc es, bool dense_rows = false,
+                      // the multisplit kernel as a persistent grid with the next unit's records in flight
+                      bool persistent = true);
 void launch_count_flags(hipStream_t s, const unsigned char* flags, i64 n, i64* blk_cnt, int nblk);
 void launch_scan_sum(hipStream_t s, i64* a, int n);
 // word_pre[w] = exclusive popcount prefix of the first-occurrence bitmap before word w (low 32 bits)

@@ -17,15 +17,22 @@ namespace shd {
 #ifdef SH_STAMPS
 constexpr int kStampKernels = 4, kStampBlocks = 32768, kStampPts = 16;
 __device__ unsigned long long g_stamps[kStampKernels * kStampBlocks * kStampPts];
-#define SH_STAMP(kern, pt)                                                                                   \
+#define SH_STAMP_AT(kern, idx, pt, WAIT)                                                                     \
     do {                                                                                                     \
-        if (threadIdx.x == 0 && blockIdx.x < kStampBlocks) {                                                 \
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                      \
-            g_stamps[((size_t)(kern) * kStampBlocks + blockIdx.x) * kStampPts + (pt)] = __builtin_amdgcn_s_memtime(); \
+        if (threadIdx.x == 0 && (idx) < kStampBlocks) {                                                      \
+            asm volatile(WAIT ::: "memory");                                                                 \
+            g_stamps[((size_t)(kern) * kStampBlocks + (idx)) * kStampPts + (pt)] = __builtin_amdgcn_s_memtime(); \
         }                                                                                                    \
     } while (0)
+#define SH_STAMP(kern, pt) SH_STAMP_AT(kern, blockIdx.x, pt, "s_waitcnt vmcnt(0) lgkmcnt(0)")
+// a persistent kernel's stamps, one set per unit of work; the _LDS form does not wait for global loads,
+// for points behind which a prefetch is meant to stay in flight
+#define SH_STAMP_UNIT(kern, unit, pt) SH_STAMP_AT(kern, unit, pt, "s_waitcnt vmcnt(0) lgkmcnt(0)")
+#define SH_STAMP_UNIT_LDS(kern, unit, pt) SH_STAMP_AT(kern, unit, pt, "s_waitcnt lgkmcnt(0)")
 #else
 #define SH_STAMP(kern, pt) do {} while (0)
+#define SH_STAMP_UNIT(kern, unit, pt) do {} while (0)
+#define SH_STAMP_UNIT_LDS(kern, unit, pt) do {} while (0)
 #endif
 
 // ================================================================================================
@@ -509,23 +516,29 @@ template <int F = SH_MAX_AGGS>
 __device__ __forceinline__ void write_row(const AggPlan& ap, u64* row, int RW, u32 pos, u32 c, u32 first, u32 last,
                                           const u64 (&f)[F], const EvSrc& es, bool have_last = false,
                                           i64 last_ts = 0, i64 last_seq = 0) {
-    u64 w[4 + SH_MAX_AGGS];
-    w[0] = (u64)pos | ((u64)c << 32);
-    w[1] = (u64)first | ((u64)last << 32);
-    // the last event's timestamp and stream index (prefetched by the caller when it could)
-    w[2] = (u64)(have_last ? last_ts : ev_ts(es, last));
-    w[3] = (u64)(have_last ? last_seq : ev_seq(es, last));
-#pragma unroll
-    for (int a = 0; a < SH_MAX_AGGS; a++) {
-        u64 fv = f[0];
-#pragma unroll
-        for (int j = 1; j < F; j++) if (ap.field[a] == j) fv = f[j];
-        w[4 + a] = a < ap.n ? agg_out(ap, a, c, fv) : 0;
-    }
+    // a pair of words is computed and stored before the next one, so that few of them are live at once
 #pragma unroll
     for (int i = 0; i < (4 + SH_MAX_AGGS) / 2; i++) {
         if (2 * i >= RW) break;
-        ((ulonglong2*)row)[i] = make_ulonglong2(w[2 * i], w[2 * i + 1]);
+        u64 w[2];
+        if (i == 0) {
+            w[0] = (u64)pos | ((u64)c << 32);
+            w[1] = (u64)first | ((u64)last << 32);
+        } else if (i == 1) {
+            // the last event's timestamp and stream index (prefetched by the caller when it could)
+            w[0] = (u64)(have_last ? last_ts : ev_ts(es, last));
+            w[1] = (u64)(have_last ? last_seq : ev_seq(es, last));
+        } else {
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int a = 2 * i - 4 + h;
+                u64 fv = f[0];
+#pragma unroll
+                for (int j = 1; j < F; j++) if (ap.field[a] == j) fv = f[j];
+                w[h] = a < ap.n ? agg_out(ap, a, c, fv) : 0;
+            }
+        }
+        ((ulonglong2*)row)[i] = make_ulonglong2(w[0], w[1]);
     }
 }
 
@@ -638,11 +651,20 @@ __global__ __launch_bounds__(kBlock) void k_aggregate_flat(const Segment* __rest
 // of the chunk (coalesced), ranks each record among its run's records of the same owner (ballots over
 // the 9 owner bits, a wave-private running count per owner), and after one workgroup scan per chunk
 // every record has its slot in its owner's list, in event order. The owner then folds its list.
+//
+// A workgroup is persistent: workgroup b takes the units (window, partition) b, b + grid, ... (the grid
+// is a multiple of 8 or the unit count, so a partition keeps its XCD). The raw loads of the chunk after
+// the current one — the unit's next chunk or the first chunk of the workgroup's next unit — are issued
+// once the current chunk's records stand in LDS (behind step (e) and the row's last-event reads), into
+// the registers the chunk has just freed, so they are in flight during the fold, the row copy-out and
+// the barriers up to the next decode. The LDS arrays are reused from chunk to chunk and unit to unit;
+// every reuse is behind a barrier (noted where it is not obvious).
 constexpr int kOwnT = 512;
 template <int V, int K, int R, int F, u32 SIG, bool PACK>
 __global__ __launch_bounds__(kOwnT, 4) void k_aggregate_own(const i64* __restrict__ seg_off, int P, int logP,
-                                                           AggPlan ap, u64* rows, int RW, u32* unit_rows,
-                                                           u32* first_bits, const Segment* __restrict__ segs,
+                                                           int n_units, AggPlan ap, u64* rows, int RW,
+                                                           u32* unit_rows, u32* first_bits,
+                                                           const Segment* __restrict__ segs,
                                                            const u32* __restrict__ rec_pos,
                                                            const u32* __restrict__ rec_idx,
                                                            const u64* __restrict__ rec_vals, i64 rec_cap, EvSrc es,
@@ -656,232 +678,320 @@ __global__ __launch_bounds__(kOwnT, 4) void k_aggregate_own(const i64* __restric
     __shared__ u32 wcnt[W][kOwnT];  // per wave: running count per owner, then its offset
     __shared__ u32 bstart[kOwnT];
     __shared__ u32 lstart[CH / 32];  // bitmap: chunk positions where an owner's list starts
+    __shared__ unsigned char has[kOwnT];
     constexpr u32 kNone = 0xFFFFFFFFu;
-    const int seg = blockIdx.x / P;
-    const int p = blockIdx.x - seg * P;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const i64 lo = seg_off[(i64)seg * P + p], hi = seg_off[(i64)(seg + 1) * P + p];
-    // packed records: the low kPackIdxBits of the event index, which lies in [seg_lo, seg_lo + 2^bits)
-    const u32 seg_lo = PACK ? (u32)segs[seg].lo : 0u;
-    SH_STAMP(0, 0);
-    u32 cnt0 = 0, fst0 = 0, lst0 = 0, cnt1 = 0, fst1 = 0, lst1 = 0;
-    i64 pf_ts = 0, pf_seq = 0;
-    bool pf = false;
-    u64 f0[F], f1[F];
-#pragma unroll
-    for (int j = 0; j < F; j++) { f0[j] = 0; f1[j] = 0; }
-    for (i64 c0 = lo; c0 < hi; c0 += CH) {
-        const int n = (int)min((i64)CH, hi - c0);
-        // (a) the wave's run of the chunk, coalesced, into registers
-        u32 li[R], ix[R];
-        i64 v[R][V];
+    const int G = (int)gridDim.x;
+    // a unit's record range and, for packed records, its segment's first event (the low kPackIdxBits
+    // of the event index, which lies in [seg_lo, seg_lo + 2^bits)); past the last unit: nothing
+    auto bounds = [&](int u, i64& lo, i64& hi, u32& slo) {
+        lo = 0; hi = 0; slo = 0;
+        if (u < n_units) {
+            lo = seg_off[u];
+            hi = seg_off[(i64)u + P];
+            if (PACK) slo = (u32)segs[u >> logP].lo;
+        }
+    };
+    // the raw loads of the wave's run of the chunk [c0, min(c0 + CH, hi)), coalesced (nothing when the
+    // chunk is empty): the packed word or the event index, the key slot, the values
+    u32 rw[R], rp[PACK ? 1 : R];
+    i64 rv[R][V];
+    auto issue = [&](i64 c0, i64 hi) {
+        const int n = (int)max((i64)0, min((i64)CH, hi - c0));
+        const u32* pi = rec_idx + c0;
+        const u32* pp = rec_pos + c0;
+        const u64* pv = rec_vals + c0;
 #pragma unroll
         for (int j = 0; j < R; j++) {
             const int r = w * PW + j * 64 + lane;
             const bool ok = r < n;
-            if (PACK) {
-                const u32 wd = ok ? rec_idx[c0 + r] : 0u;
-                li[j] = ok ? (wd >> kPackIdxBits) : kNone;
-                ix[j] = seg_lo + (((wd & kPackIdxMask) - seg_lo) & kPackIdxMask);
-            } else {
-                li[j] = ok ? (rec_pos[c0 + r] >> logP) : kNone;
-                ix[j] = ok ? rec_idx[c0 + r] : 0;
-            }
+            rw[j] = ok ? pi[r] : 0u;
+            if (!PACK) rp[j] = ok ? pp[r] : 0u;
 #pragma unroll
-            for (int x = 0; x < V; x++) v[j][x] = (ok && x < ap.n_vcols) ? (i64)rec_vals[(size_t)x * rec_cap + c0 + r] : 0;
+            for (int x = 0; x < V; x++) rv[j][x] = (ok && x < ap.n_vcols) ? (i64)pv[(size_t)x * rec_cap + r] : 0;
         }
-        SH_STAMP(0, 1);
-        // (b) rank among the run's records of the same owner: a wave-private running count per owner,
-        // advanced by LDS atomics (the wave's rounds complete in program order; lanes of one round
-        // that share an owner get distinct ranks, in an order (e) restores)
+    };
+    i64 lo, hi, nlo, nhi, nnlo = 0, nnhi = 0;
+    u32 seg_lo, nseg_lo, nnseg_lo = 0;
+    bounds((int)blockIdx.x, lo, hi, seg_lo);
+    bounds((int)blockIdx.x + G, nlo, nhi, nseg_lo);
+    issue(lo, hi);
+    for (int unit = blockIdx.x; unit < n_units; unit += G) {
+        const int p = unit & (P - 1);
+        SH_STAMP_UNIT_LDS(0, unit, 0);
+        u32 cnt0 = 0, fst0 = 0, lst0 = 0, cnt1 = 0, fst1 = 0, lst1 = 0;
+        i64 pf_ts = 0, pf_seq = 0;
+        bool pf = false;
+        u64 f0[F], f1[F];
 #pragma unroll
-        for (int i = lane; i < kOwnT; i += 64) wcnt[w][i] = 0;
-        for (int i = t; i < CH / 32; i += kOwnT) lstart[i] = 0;
+        for (int j = 0; j < F; j++) { f0[j] = 0; f1[j] = 0; }
+        i64 c0 = lo;
+        do {
+            const int n = (int)max((i64)0, min((i64)CH, hi - c0));
+            const bool last = c0 + CH >= hi;
+            // (a) the wave's run of the chunk, loaded one chunk ahead, into the working registers
+            u32 li[R], ix[R];
+            i64 v[R][V];
 #pragma unroll
-        for (int j = 0; j < R; j++) {
-            if (li[j] == kNone) continue;
-            const u32 rk = atomicAdd(&wcnt[w][li[j] & (kOwnT - 1)], 1u);
-            // local key (< 1024) and its rank (< CH <= 4096) share the register from here on
-            li[j] |= rk << 10;
-        }
-        __syncthreads();
-        SH_STAMP(0, 2);
-        // (c) owner t: offsets of the waves' runs in its list, then its list's start in the chunk
-        u32 tot = 0;
-#pragma unroll
-        for (int x = 0; x < W; x++) {
-            const u32 c = wcnt[x][t];
-            wcnt[x][t] = tot;
-            tot += c;
-        }
-        i64 all;
-        const u32 start = (u32)block_excl_scan_any((i64)tot, &all);
-        bstart[t] = start;
-        if (tot) atomicOr(&lstart[start >> 5], 1u << (start & 31));
-        __syncthreads();
-        // (d) every record into its owner's list
-#pragma unroll
-        for (int j = 0; j < R; j++) {
-            if (li[j] == kNone) continue;
-            const u32 b = li[j] & (kOwnT - 1);
-            const u32 d = bstart[b] + wcnt[w][b] + (li[j] >> 10);
-            st_idx[d] = ix[j];
-#pragma unroll
-            for (int x = 0; x < V; x++) st_v[x][d] = (u64)v[j][x];
-            if (K > 1) st_hi[d] = (unsigned char)((li[j] >> 9) & 1);
-        }
-        __syncthreads();
-        SH_STAMP(0, 3);
-        // (e) the owner's list is in event order unless lanes of one round that shared the owner got
-        // their ranks out of lane order (never seen on gfx950: scripts/probe/lds_atomic_order.hip);
-        // checked in parallel over adjacent positions of one list, repaired by an insertion pass
-        bool bad = false;
-        for (int d = t; d + 1 < n; d += kOwnT)
-            bad |= !((lstart[(d + 1) >> 5] >> ((d + 1) & 31)) & 1u) && st_idx[d + 1] < st_idx[d];
-        if (__syncthreads_or(bad) && tot > 1) {
-            u32 prev = st_idx[start];
-            for (u32 k = 1; k < tot; k++) {
-                const u32 e = st_idx[start + k];
-                if (e > prev) { prev = e; continue; }
-                u64 mv[V];
-#pragma unroll
-                for (int x = 0; x < V; x++) mv[x] = st_v[x][start + k];
-                const unsigned char mh = K > 1 ? st_hi[start + k] : 0;
-                u32 m = k;
-                while (m > 0 && st_idx[start + m - 1] > e) {
-                    st_idx[start + m] = st_idx[start + m - 1];
-#pragma unroll
-                    for (int x = 0; x < V; x++) st_v[x][start + m] = st_v[x][start + m - 1];
-                    if (K > 1) st_hi[start + m] = st_hi[start + m - 1];
-                    m--;
+            for (int j = 0; j < R; j++) {
+                const int r = w * PW + j * 64 + lane;
+                const bool ok = r < n;
+                if (PACK) {
+                    const u32 wd = rw[j];
+                    li[j] = ok ? (wd >> kPackIdxBits) : kNone;
+                    ix[j] = seg_lo + (((wd & kPackIdxMask) - seg_lo) & kPackIdxMask);
+                } else {
+                    li[j] = ok ? (rp[j] >> logP) : kNone;
+                    ix[j] = rw[j];
                 }
-                st_idx[start + m] = e;
 #pragma unroll
-                for (int x = 0; x < V; x++) st_v[x][start + m] = mv[x];
-                if (K > 1) st_hi[start + m] = mh;
+                for (int x = 0; x < V; x++) v[j][x] = rv[j][x];
             }
-        }
-        SH_STAMP(0, 4);
-        // the unit's last chunk: the owner's last event is its list's last entry (one key per owner
-        // when K == 1), so the random reads of that event's timestamp and stream index for the row
-        // are issued now and complete while the list is folded
-        if (K == 1 && c0 + CH >= hi && tot) {
-            const u32 el = st_idx[start + tot - 1];
-            pf_ts = ev_ts(es, el);
-            pf_seq = ev_seq(es, el);
-            pf = true;
-        }
-        // then folds it; the next record's LDS loads are issued before the current one is folded, so
-        // their latency overlaps the fold
-        u32 e_nx = 0;
-        i64 v_nx[V];
-        unsigned char hi_nx = 0;
+            SH_STAMP_UNIT(0, unit, 1);
+            u32 tot = 0, start = 0;
+            if (n > 0) {
+                // (b) rank among the run's records of the same owner: a wave-private running count per
+                // owner, advanced by LDS atomics (the wave's rounds complete in program order; lanes of
+                // one round that share an owner get distinct ranks, in an order (e) restores).
+                // (wcnt and lstart were last read in (d) and (e) of the chunk before: barriers since)
 #pragma unroll
-        for (int x = 0; x < V; x++) v_nx[x] = 0;
-        if (tot) {
-            e_nx = st_idx[start];
+                for (int i = lane; i < kOwnT; i += 64) wcnt[w][i] = 0;
+                for (int i = t; i < CH / 32; i += kOwnT) lstart[i] = 0;
 #pragma unroll
-            for (int x = 0; x < V; x++) if (x < ap.n_vcols) v_nx[x] = (i64)st_v[x][start];
-            if (K > 1) hi_nx = st_hi[start];
-        }
-        for (u32 k = 0; k < tot; k++) {
-            const u32 e = e_nx;
-            i64 vv[V];
+                for (int j = 0; j < R; j++) {
+                    if (li[j] == kNone) continue;
+                    const u32 rk = atomicAdd(&wcnt[w][li[j] & (kOwnT - 1)], 1u);
+                    // local key (< 1024) and its rank (< CH <= 4096) share the register from here on
+                    li[j] |= rk << 10;
+                }
+                __syncthreads();
+                SH_STAMP_UNIT_LDS(0, unit, 2);
+                // (c) owner t: offsets of the waves' runs in its list, then its list's start in the chunk
 #pragma unroll
-            for (int x = 0; x < V; x++) vv[x] = v_nx[x];
-            const unsigned char hi_cur = hi_nx;
-            if (k + 1 < tot) {
-                const u32 i = start + k + 1;
-                e_nx = st_idx[i];
+                for (int x = 0; x < W; x++) {
+                    const u32 c = wcnt[x][t];
+                    wcnt[x][t] = tot;
+                    tot += c;
+                }
+                i64 all;
+                start = (u32)block_excl_scan_any((i64)tot, &all);
+                bstart[t] = start;
+                if (tot) atomicOr(&lstart[start >> 5], 1u << (start & 31));
+                __syncthreads();
+                // (d) every record into its owner's list (st_*: the fold of the chunk before and the row
+                // copy-out of the unit before read them ahead of the two barriers above)
 #pragma unroll
-                for (int x = 0; x < V; x++) if (x < ap.n_vcols) v_nx[x] = (i64)st_v[x][i];
-                if (K > 1) hi_nx = st_hi[i];
+                for (int j = 0; j < R; j++) {
+                    if (li[j] == kNone) continue;
+                    const u32 b = li[j] & (kOwnT - 1);
+                    const u32 d = bstart[b] + wcnt[w][b] + (li[j] >> 10);
+                    st_idx[d] = ix[j];
+#pragma unroll
+                    for (int x = 0; x < V; x++) st_v[x][d] = (u64)v[j][x];
+                    if (K > 1) st_hi[d] = (unsigned char)((li[j] >> 9) & 1);
+                }
+                __syncthreads();
+                SH_STAMP_UNIT_LDS(0, unit, 3);
+                // (e) the owner's list is in event order unless lanes of one round that shared the owner
+                // got their ranks out of lane order (never seen on gfx950:
+                // scripts/probe/lds_atomic_order.hip); checked in parallel over adjacent positions of one
+                // list, repaired by an insertion pass
+                bool bad = false;
+                for (int d = t; d + 1 < n; d += kOwnT)
+                    bad |= !((lstart[(d + 1) >> 5] >> ((d + 1) & 31)) & 1u) && st_idx[d + 1] < st_idx[d];
+                if (__syncthreads_or(bad) && tot > 1) {
+                    u32 prev = st_idx[start];
+                    for (u32 k = 1; k < tot; k++) {
+                        const u32 e = st_idx[start + k];
+                        if (e > prev) { prev = e; continue; }
+                        u64 mv[V];
+#pragma unroll
+                        for (int x = 0; x < V; x++) mv[x] = st_v[x][start + k];
+                        const unsigned char mh = K > 1 ? st_hi[start + k] : 0;
+                        u32 m = k;
+                        while (m > 0 && st_idx[start + m - 1] > e) {
+                            st_idx[start + m] = st_idx[start + m - 1];
+#pragma unroll
+                            for (int x = 0; x < V; x++) st_v[x][start + m] = st_v[x][start + m - 1];
+                            if (K > 1) st_hi[start + m] = st_hi[start + m - 1];
+                            m--;
+                        }
+                        st_idx[start + m] = e;
+#pragma unroll
+                        for (int x = 0; x < V; x++) st_v[x][start + m] = mv[x];
+                        if (K > 1) st_hi[start + m] = mh;
+                    }
+                }
+                SH_STAMP_UNIT_LDS(0, unit, 4);
+                // the unit's last chunk: the owner's last event is its list's last entry (one key per
+                // owner when K == 1), so the random reads of that event's timestamp and stream index for
+                // the row are issued now and complete while the list is folded
+                if (K == 1 && last && tot) {
+                    const u32 el = st_idx[start + tot - 1];
+                    pf_ts = ev_ts(es, el);
+                    pf_seq = ev_seq(es, el);
+                    pf = true;
+                }
             }
-            if (K > 1 && hi_cur) {
-                fold_fields<V, F, SIG>(ap, f1, cnt1 == 0, vv);
-                if (cnt1 == 0) fst1 = e;
-                lst1 = e;
-                cnt1++;
+            // The records are in LDS and their registers free: the next chunk's loads go out here, behind
+            // the row's two reads (which the row then waits for alone), and stay in flight through the
+            // fold, the row copy-out and the barriers up to the next decode. It is the unit's next chunk,
+            // or the first chunk of the workgroup's next unit, whose bounds were read one unit earlier (as
+            // the one after it is now). (Issued before (b), into registers beside the working set, the C2
+            // instantiation needs 35 registers more than the 128 that two workgroups per CU leave it.)
+            issue(last ? nlo : c0 + CH, last ? nhi : hi);
+            if (last) bounds(unit + 2 * G, nnlo, nnhi, nnseg_lo);
+            {
+                // then folds it; the next record's LDS loads are issued before the current one is folded,
+                // so their latency overlaps the fold
+                u32 e_nx = 0;
+                i64 v_nx[V];
+                unsigned char hi_nx = 0;
+#pragma unroll
+                for (int x = 0; x < V; x++) v_nx[x] = 0;
+                if (tot) {
+                    e_nx = st_idx[start];
+#pragma unroll
+                    for (int x = 0; x < V; x++) if (x < ap.n_vcols) v_nx[x] = (i64)st_v[x][start];
+                    if (K > 1) hi_nx = st_hi[start];
+                }
+                for (u32 k = 0; k < tot; k++) {
+                    const u32 e = e_nx;
+                    i64 vv[V];
+#pragma unroll
+                    for (int x = 0; x < V; x++) vv[x] = v_nx[x];
+                    const unsigned char hi_cur = hi_nx;
+                    if (k + 1 < tot) {
+                        const u32 i = start + k + 1;
+                        e_nx = st_idx[i];
+#pragma unroll
+                        for (int x = 0; x < V; x++) if (x < ap.n_vcols) v_nx[x] = (i64)st_v[x][i];
+                        if (K > 1) hi_nx = st_hi[i];
+                    }
+                    if (K > 1 && hi_cur) {
+                        fold_fields<V, F, SIG>(ap, f1, cnt1 == 0, vv);
+                        if (cnt1 == 0) fst1 = e;
+                        lst1 = e;
+                        cnt1++;
+                    } else {
+                        fold_fields<V, F, SIG>(ap, f0, cnt0 == 0, vv);
+                        if (cnt0 == 0) fst0 = e;
+                        lst0 = e;
+                        cnt0++;
+                    }
+                }
+            }
+            c0 += CH;
+        } while (c0 < hi);
+        SH_STAMP_UNIT_LDS(0, unit, 5);
+        // one row per key with events, in the unit's own region of K * 512 row slots (no global counter:
+        // a contended atomic on one address would serialise every workgroup of the launch)
+        const int mine = (cnt0 > 0) + (K > 1 && cnt1 > 0);
+        i64 tot;
+        // The scan's two barriers, the second one behind its last LDS read, are also what orders the LDS
+        // reuse of the epilogue: the fold's reads of st_v before the row staging below, and the copy-out
+        // (st_v, has[]) of the unit before — which an empty unit follows with no chunk-loop barrier in
+        // between — before this unit's writes. A scan without its trailing barrier would need one here.
+        const i64 pre = block_excl_scan_any((i64)mine, &tot);
+        if (t == 0) unit_rows[unit] = (u32)tot;
+        const u64 base = (u64)unit * (u64)(K * kOwnT);
+        const bool staged = K == 1 && (size_t)kOwnT * RW * 8 <= sizeof(st_v);
+        if (dense) {
+            // rows at their local key's slot of the unit (K * kOwnT rows, holes where a key had no
+            // event): the emission finds a row from its first event's key slot, no rank scatter
+            // (k_emit_gather)
+            if (cnt0) mark_first(first_bits, fst0);
+            if (K > 1 && cnt1) mark_first(first_bits, fst1);
+            if (staged) {
+                // (the scan's barriers stand between the fold's reads of st_v and these writes, and
+                // between the copy-out of the unit before and has[])
+                u64* stg = &st_v[0][0];
+                has[t] = cnt0 > 0;
+                if (cnt0)
+                    write_row<F>(ap, stg + (size_t)t * RW, RW, ((u32)t << logP) | (u32)p, cnt0, fst0, lst0, f0, es, pf,
+                                 pf_ts, pf_seq);
+                __syncthreads();
+                const int h = RW / 2, n2 = kOwnT * h;
+                ulonglong2* dst = (ulonglong2*)(rows + base * RW);
+                const ulonglong2* src = (const ulonglong2*)stg;
+                for (int i = t; i < n2; i += kOwnT)
+                    if (has[i / h]) dst[i] = src[i];
             } else {
-                fold_fields<V, F, SIG>(ap, f0, cnt0 == 0, vv);
-                if (cnt0 == 0) fst0 = e;
-                lst0 = e;
-                cnt0++;
+                if (cnt0)
+                    write_row<F>(ap, rows + (base + (u64)t) * RW, RW, ((u32)t << logP) | (u32)p, cnt0, fst0, lst0, f0, es,
+                                 pf, pf_ts, pf_seq);
+                if (K > 1 && cnt1)
+                    write_row<F>(ap, rows + (base + (u64)(t + kOwnT)) * RW, RW, ((u32)(t + kOwnT) << logP) | (u32)p, cnt1,
+                                 fst1, lst1, f1, es);
+            }
+        } else {
+            if (cnt0) mark_first(first_bits, fst0);
+            if (K > 1 && cnt1) mark_first(first_bits, fst1);
+            if (staged) {
+                // the unit's rows are one contiguous run: staged in LDS (the record staging is free
+                // now), then stored with whole-line writes instead of each thread's strided 16-byte pieces
+                u64* stg = &st_v[0][0];
+                if (cnt0)
+                    write_row<F>(ap, stg + (size_t)pre * RW, RW, ((u32)t << logP) | (u32)p, cnt0, fst0, lst0, f0, es, pf,
+                                 pf_ts, pf_seq);
+                __syncthreads();
+                const int n2 = (int)tot * RW / 2;
+                ulonglong2* dst = (ulonglong2*)(rows + base * RW);
+                const ulonglong2* src = (const ulonglong2*)stg;
+                for (int i = t; i < n2; i += kOwnT) dst[i] = src[i];
+            } else {
+                u32 r = (u32)base + (u32)pre;
+                if (cnt0) {
+                    write_row<F>(ap, rows + (size_t)r * RW, RW, ((u32)t << logP) | (u32)p, cnt0, fst0, lst0, f0, es, pf,
+                                 pf_ts, pf_seq);
+                    r++;
+                }
+                if (K > 1 && cnt1)
+                    write_row<F>(ap, rows + (size_t)r * RW, RW, ((u32)(t + kOwnT) << logP) | (u32)p, cnt1, fst1, lst1, f1,
+                                 es);
             }
         }
+        SH_STAMP_UNIT_LDS(0, unit, 6);
+        lo = nlo; hi = nhi; seg_lo = nseg_lo;
+        nlo = nnlo; nhi = nnhi; nseg_lo = nnseg_lo;
     }
-    SH_STAMP(0, 5);
-    // one row per key with events, in the unit's own region of K * 512 row slots (no global counter:
-    // a contended atomic on one address would serialise every workgroup of the launch)
-    const int mine = (cnt0 > 0) + (K > 1 && cnt1 > 0);
-    i64 tot;
-    const i64 pre = block_excl_scan_any((i64)mine, &tot);
-    if (t == 0) unit_rows[blockIdx.x] = (u32)tot;
-    if (dense) {
-        // rows at their local key's slot of the unit (K * kOwnT rows, holes where a key had no event):
-        // the emission finds a row from its first event's key slot, no rank scatter (k_emit_gather)
-        const u64 base = (u64)blockIdx.x * (u64)(K * kOwnT);
-        if (K == 1 && (size_t)kOwnT * RW * 8 <= sizeof(st_v)) {
-            u64* stg = &st_v[0][0];
-            __shared__ unsigned char has[kOwnT];
-            __syncthreads();
-            has[t] = cnt0 > 0;
-            if (cnt0) {
-                write_row<F>(ap, stg + (size_t)t * RW, RW, ((u32)t << logP) | (u32)p, cnt0, fst0, lst0, f0, es, pf, pf_ts,
-                             pf_seq);
-                mark_first(first_bits, fst0);
-            }
-            __syncthreads();
-            const int h = RW / 2, n2 = kOwnT * h;
-            ulonglong2* dst = (ulonglong2*)(rows + base * RW);
-            const ulonglong2* src = (const ulonglong2*)stg;
-            for (int i = t; i < n2; i += kOwnT)
-                if (has[i / h]) dst[i] = src[i];
-            SH_STAMP(0, 6);
-            return;
-        }
-        if (cnt0) {
-            write_row<F>(ap, rows + (base + (u64)t) * RW, RW, ((u32)t << logP) | (u32)p, cnt0, fst0, lst0, f0, es, pf,
-                         pf_ts, pf_seq);
-            mark_first(first_bits, fst0);
-        }
-        if (K > 1 && cnt1) {
-            write_row<F>(ap, rows + (base + (u64)(t + kOwnT)) * RW, RW, ((u32)(t + kOwnT) << logP) | (u32)p, cnt1, fst1,
-                         lst1, f1, es);
-            mark_first(first_bits, fst1);
-        }
-        SH_STAMP(0, 6);
-        return;
+}
+
+// The persistent fold's grid: the workgroups resident at once, rounded down to a multiple of 8 so that
+// a unit's partition keeps its XCD from one unit of a workgroup to the next (0: not known, one workgroup
+// per unit). Taken once per instantiation from the device that is current at the first launch: the GPUs of
+// one process are the same model (§7), and a different count would cost speed, never a result — any grid
+// from 1 to the unit count covers every unit.
+template <int V, int K, int R, int F, u32 SIG, bool PACK>
+static int own_resident_grid() {
+    static const int g = [] {
+        int per_cu = 0, dev = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_aggregate_own<V, K, R, F, SIG, PACK>, kOwnT, 0) !=
+                hipSuccess ||
+            hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            return 0;
+        return (per_cu * cus) & ~7;
+    }();
+    return g;
+}
+
+// `persistent`: a grid of the resident workgroups, each taking every grid-th unit with the next unit's
+// records in flight; otherwise one workgroup per unit (the same kernel, whose prefetch finds no next unit).
+// Only the one-value-column instantiations take the grid: it is where it was measured to win (C2: the fold
+// 316 -> 293 us); with two value columns (C1's lengthBatch windows, two short chunks per unit) the grid
+// measured 186 against 181 us, so those and the wider ones keep the hardware's dispatch.
+template <int V, int K, int R, int F, u32 SIG, bool PACK>
+static void launch_own(hipStream_t s, int n_units, bool persistent, const i64* seg_off, int P, int logP, AggPlan ap,
+                       u64* rows, int RW, u32* unit_rows, u32* first_bits, const Segment* segs,
+                       const u32* rec_pos, const u32* rec_idx, const u64* rec_vals, i64 rec_cap, EvSrc es, int dense) {
+    int grid = n_units;
+    if (persistent && V == 1) {
+        const int g = own_resident_grid<V, K, R, F, SIG, PACK>();
+        if (g > 0) grid = std::min(g, n_units);
     }
-    u32 r = (u32)blockIdx.x * (u32)(K * kOwnT) + (u32)pre;
-    if (K == 1 && (size_t)kOwnT * RW * 8 <= sizeof(st_v)) {
-        // the unit's rows are one contiguous run: staged in LDS (the record staging is free now),
-        // then stored with whole-line writes instead of each thread's strided 16-byte pieces
-        u64* stg = &st_v[0][0];
-        __syncthreads();
-        if (cnt0)
-            write_row<F>(ap, stg + (size_t)pre * RW, RW, ((u32)t << logP) | (u32)p, cnt0, fst0, lst0, f0, es, pf, pf_ts,
-                         pf_seq);
-        if (cnt0) mark_first(first_bits, fst0);
-        __syncthreads();
-        const int n2 = (int)tot * RW / 2;
-        ulonglong2* dst = (ulonglong2*)(rows + (size_t)blockIdx.x * (K * kOwnT) * RW);
-        const ulonglong2* src = (const ulonglong2*)stg;
-        for (int i = t; i < n2; i += kOwnT) dst[i] = src[i];
-        SH_STAMP(0, 6);
-        return;
-    }
-    if (cnt0) {
-        write_row<F>(ap, rows + (size_t)r * RW, RW, ((u32)t << logP) | (u32)p, cnt0, fst0, lst0, f0, es, pf, pf_ts,
-                     pf_seq);
-        mark_first(first_bits, fst0);
-        r++;
-    }
-    if (K > 1 && cnt1) {
-        write_row<F>(ap, rows + (size_t)r * RW, RW, ((u32)(t + kOwnT) << logP) | (u32)p, cnt1, fst1, lst1, f1, es);
-        mark_first(first_bits, fst1);
-    }
-    SH_STAMP(0, 6);
+    hipLaunchKernelGGL((k_aggregate_own<V, K, R, F, SIG, PACK>), dim3(grid), dim3(kOwnT), 0, s, seg_off, P, logP, n_units,
+                       ap, rows, RW, unit_rows, first_bits, segs, rec_pos, rec_idx, rec_vals, rec_cap, es, dense);
 }
 
 int own_keys_per_thread(int NL) { return NL <= kOwnT ? 1 : 2; }
@@ -892,7 +1002,7 @@ void launch_aggregate(hipStream_t s, const Segment* segs, int nseg, int P, int l
                       const u32* pend_pos, const u64* pend_vals, i64 pend_cap, const u32* new_pos, ColSet cols,
                       AggPlan ap, u64* rows, int RW, u32* unit_rows, u32* first_bits,
                       const u32* rec_pos, const u32* rec_idx, const u64* rec_vals, i64 rec_cap, const i64* seg_off,
-                      bool pack, EvSrc es, bool dense_rows) {
+                      bool pack, EvSrc es, bool dense_rows, bool persistent) {
     const int dense = dense_rows ? 1 : 0;
     if (rec_idx) {  // multisplit records: thread-ownership kernel
         const int K = own_keys_per_thread(NL);
@@ -900,13 +1010,13 @@ void launch_aggregate(hipStream_t s, const Segment* segs, int nseg, int P, int l
 #define SH_AGG_OWN(VV, KK, RR, FF, SG)                                                                          \
     do {                                                                                                        \
         if (pack)                                                                                               \
-            hipLaunchKernelGGL((k_aggregate_own<VV, KK, RR, FF, SG, true>), dim3(nseg * P), dim3(kOwnT), 0, s,   \
-                               seg_off, P, logP, ap, rows, RW, unit_rows, first_bits, segs, rec_pos, rec_idx,    \
-                               rec_vals, rec_cap, es, dense);                                                   \
+            launch_own<VV, KK, RR, FF, SG, true>(s, nseg * P, persistent, seg_off, P, logP, ap, rows, RW,        \
+                                                 unit_rows, first_bits, segs, rec_pos, rec_idx,                  \
+                                                 rec_vals, rec_cap, es, dense);                                 \
         else                                                                                                    \
-            hipLaunchKernelGGL((k_aggregate_own<VV, KK, RR, FF, SG, false>), dim3(nseg * P), dim3(kOwnT), 0, s,  \
-                               seg_off, P, logP, ap, rows, RW, unit_rows, first_bits, segs, rec_pos, rec_idx,    \
-                               rec_vals, rec_cap, es, dense);                                                   \
+            launch_own<VV, KK, RR, FF, SG, false>(s, nseg * P, persistent, seg_off, P, logP, ap, rows, RW,       \
+                                                  unit_rows, first_bits, segs, rec_pos, rec_idx,                 \
+                                                  rec_vals, rec_cap, es, dense);                                \
     } while (0)
 #define SH_AGG_OWN_F(VV, KK, RR)                          \
     do {                                                  \

@@ -236,6 +236,8 @@ Tuning Tuning::from_env() {
     t.slx_wave = !getenv("SH_SLX_WAVE") || on("SH_SLX_WAVE");
     // a large push's independent small kernels beside the big passes; SH_SIDE_STREAM=0: one stream
     t.side_stream = !getenv("SH_SIDE_STREAM") || on("SH_SIDE_STREAM");
+    // the multisplit fold as a persistent grid; =0 puts back one workgroup per unit, for A/B runs and bisecting
+    t.fold_grid = !getenv("SH_FOLD_GRID") || on("SH_FOLD_GRID");
     return t;
 }
 

@@ -231,9 +231,11 @@ struct SlidingImpl;
 // A/B switches of the measured alternatives, read from the environment once per query,
 // when it is created, so a process can run queries with different settings side by side:
 // SH_DIRECT_POS=1, SH_PART_KEYS=1024, SH_NO_ASYNC_SMALL=1, SH_SL_RECORDS_SEQ=0/1, SH_AGG_BAND_ROWS=n,
-// SH_SIDE_STREAM=0 (a large push's bookkeeping back on the one stream, compaction in place)
+// SH_SIDE_STREAM=0 (a large push's bookkeeping back on the one stream, compaction in place),
+// SH_FOLD_GRID=0 (the multisplit fold with one workgroup per unit instead of a persistent grid)
 struct Tuning {
     bool side_stream = true;
+    bool fold_grid = true;
     bool direct_pos = false, part_keys_1024 = false, no_async_small = false, sl_records_seq = false;
     bool pl_sort = true;   // partitioned lengthBatch keyed by the partition on the sorted lanes (lane 3)
     bool slx_wave = true;     // expired / all-events sliding replay with a wave per key (k_slx_wkey); SH_SLX_WAVE=0: a lane per key

@@ -633,7 +633,7 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
                      q->rec_packed,
                      EvSrc{q->n_pend, q->pend_ts.as<int64_t>(), ts, q->pend_gidx.as<u64>(),
                            q->given && b ? q->given_gidx : nullptr, q->seq},
-                     gather);
+                     gather, q->tune.fold_grid);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(q->ev_agg1, s));
     // output columns sized for the row capacity; the emit kernels read the row count on the device
@@ -1579,8 +1579,9 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
             // are on the device since the host read the boundaries); the sets change places below
             RCHK(grow_spare(q, new_pend));
             hipStream_t ss = q->ctx->side_stream;
-            // (beside the fold, whose workgroups leave room on every CU, not beside the bandwidth-bound
-            // k_ms_scatter: there the two slowed each other down, 48 us + 10 us against 24 us alone)
+            // (beside the fold, not beside the bandwidth-bound k_ms_scatter: there the two slowed each other
+            // down, 48 us + 10 us against 24 us alone. Under the fold's resident grid it gets what the CUs
+            // have left and ends with the fold; the main stream waits for it only behind the emission)
             HIPCHK(hipStreamWaitEvent(ss, q->ev_agg0, 0));
             launch_compact_pending(ss, b->ts, cs, pos_src(q, b), q->ap, e_lo, N, pcb_lo, 0, q->blk_pass.as<int64_t>(),
                                    q->sp_pos.as<u32>(), q->sp_ts.as<int64_t>(), q->sp_vals.as<u64>(), q->sp_cap, nullptr,
