@@ -233,7 +233,7 @@ static int sliding_rekey(sh_query* q) {
     return SH_OK;
 }
 
-// the key-sorted replay with 48-byte records (k_sl_wkey<AOS>): time windows of the count / sum / avg
+// the key-sorted replay with 48-byte records (k_sl_wkey): time windows of the count / sum / avg
 // / min / max-of-one-double shape with a min or max (sliding_keyed_ok)
 static bool keyed_aos(const sh_query* q) { return q->d.window == SH_WIN_TIME && sliding_keyed_ok(q->ap); }
 
@@ -406,7 +406,7 @@ static int sliding_finish(sh_query* q, int64_t M, int64_t rec_cap, int64_t need,
         SlRows rows{s->rows_ts.as<int64_t>(), s->rows_rep.as<u32>(), s->rows_slot.as<u32>(), s->rows_send.as<int64_t>(),
                     s->rows_clock.as<int64_t>(), s->rows_vals.as<u64>(), s->rows_nulls.as<unsigned char>(), M};
         // the common shape (count / sum / avg / min / max of one double column, time window): records
-        // sorted stably by key, one lane per key (k_sl_key); other shapes: key-partition replay
+        // sorted stably by key, one wave per key (k_sl_wkey); other shapes: key-partition replay
         if (keyed) {
             if (!presorted) {  // (presorted: sorted and key offsets made before the push's sync, sliding_push)
                 HIPCHK(hipEventRecord(q->ev_agg0, st));  // the sort is part of the replay's time

@@ -1,4 +1,6 @@
-// sh_sliding.h — device structures of the sliding time-window path (sh_sliding_kernels.hip).
+// sh_sliding.h — device structures and launches of the sliding time-window path: sh_sliding_kernels.hip
+// (records, partition replays, emit, flush, rekey), sh_sliding_wkey.hip (the keyed replay of current rows),
+// sh_slx_kernels.hip (expired / all-events output).
 #pragma once
 #include "sh_internal.h"
 
@@ -67,8 +69,9 @@ void launch_counts_sorted(hipStream_t s, const u32* ps, i64 M, u32* slot_cnt);
 void launch_sl_multisplit(hipStream_t s, const u32* slot, i64 n, int P, i64* counts, i64* tmp, u32* out_rank,
                           i64* part_off);
 int sliding_keys_per_partition(AggPlan ap);
-// key-sorted replay (k_sl_key) for the count / sum / avg / min / max-of-one-double shape: ranks =
-// the records' ranks sorted stably by slot (sort_slot_ranks, sh_sort.hip); key_off [nslots + 1]
+// ---- key-sorted replay of current rows, one wave per key (k_sl_wkey, sh_sliding_wkey.hip), for the
+// count / sum / avg / min / max-of-one-double shape with a min or max: ranks = the records' ranks sorted
+// stably by slot (sort_slot_ranks, sh_sort.hip); key_off [nslots + 1]
 bool sliding_keyed_ok(AggPlan ap);
 int sort_slot_ranks(void* temp, size_t* bytes, const u32* slot, u32* slot_out, u32* rank_out, i64 M, i64 nslots,
                     hipStream_t s);
@@ -84,6 +87,7 @@ void launch_slk_emit(hipStream_t s, const unsigned char* flags, i64 n, const i64
                      i64* out_keys, u64* out_vals, unsigned char* out_nulls, i64* out_send, i64* out_clock,
                      const u32* rank_raw, i64 raw_base, i64* out_order, i64* out_rep, const u64* aos = nullptr,
                      const u32* rank_slot = nullptr);
+// ---- partition replays, emit, flush, rekey (sh_sliding_kernels.hip)
 void launch_sl_gather(hipStream_t s, const u32* ranks, i64 M, SlRecords rec, SlRecords out, int nv);
 // rec: the records gathered into partition order (k_sl_own); rec_by_rank: the same records in rank
 // order, read through rank_list by k_sl_own_d (sliding_keys_per_partition(ap) == 8 shapes)
@@ -156,8 +160,8 @@ void launch_slx_walk(hipStream_t s, const u32* key_off, const u32* sorted_rank, 
                      const u64* aop, const u64* xop, const i64* xch, const i64* xts, const i64* xclk, const i64* useq,
                      i64 n_u, i64 X0, i64 G0, i64 seq_base, i64 send_size, SlState S, i64* rg, AggPlan ap, int cur_on,
                      int exp_on, SlxRows rows, unsigned char* flags, const i64* rsclk);
-// the same replay with one wave per key (sh_sliding_kernels.hip) for the count / sum / avg / min / max of
-// one double column shape (slx_keyed_ok)
+// the same replay with one wave per key (k_slx_wkey) for the count / sum / avg / min / max of one double
+// column shape (slx_keyed_ok)
 bool slx_keyed_ok(AggPlan ap);
 // xa: per record {aop, value, ts, clock, raw, pm}; xx: per window position {xop, value (this push's
 // records), ts, clock, event, chunk} (k_slx_aop / k_slx_expiry with their record outputs)

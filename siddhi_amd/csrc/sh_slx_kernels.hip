@@ -18,6 +18,7 @@
 // operation sequence arithmetically, and one lane per key replays its adds and removes in that order.
 #include "sh_device.h"
 #include "sh_sliding.h"
+#include "sh_sliding_wave.h"
 
 namespace shd {
 
@@ -779,6 +780,429 @@ void launch_slx_rekey_map(hipStream_t s, i64 size, KeyTable old_kt, KeyTable new
                           const u64* f, i64 nslots, AggPlan ap, u32* map) {
     hipLaunchKernelGGL(k_slx_rekey_map, dim3((unsigned)((size + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, size,
                        old_kt, new_kt, rlen, cnt, f, nslots, ap, map);
+}
+
+// ---- `insert expired / all events`, one wave per key (round 5) ----------------------------------------
+// k_slx_walk gives every key one lane that merges its adds and removes one dependent load at a time
+// (c3all: 148 ms per push). Here the 64 lanes of a wave take a key's next 64 operations at once: the
+// next 64 adds (its records in arrival order, each with its operation index aop) and the next 64
+// removes (its FIFO entries, each with the operation index xop of its expiry point, kNoOp when it
+// stays) are staged, and every staged operation finds its place in the merged order by a binary
+// search over the other list; the first 64 places form the chunk. Per operation t the window is the
+// FIFO range [head(t), end(t)), both counted by ballots, so the count is closed-form; the Java-order
+// double sum is one operation list added up from LDS (a remove as the negated value, the canDestroy
+// restart where the count reaches 0); the min / max is the range best of [head(t), end(t)) while the
+// reference's deque quirk cannot show (the check and deque bookkeeping of sh_sliding_wave.h), else the
+// deque runs sequentially for the rest of the push. Rows: one per (chunk, key), opened by its first
+// qualifying operation (the row's place = that operation's index) and holding the values after its last
+// one — the lanes are segmented by their chunk, a row still open at the chunk's end is written and
+// overwritten by the next chunk. TimeWindowProcessor.java:132-169; QuerySelector.java:315-374.
+#ifdef SH_XW_WPE
+#define SH_XW_ATTR __attribute__((amdgpu_waves_per_eu(SH_XW_WPE)))
+#else
+#define SH_XW_ATTR
+#endif
+
+// The aggregator words w[5 ..] of a row record from the values after its last operation (fl: bit 0 min
+// present, bit 1 max present) and the row's null mask: sum, avg, min and max are null at count 0; null
+// words and the padding are 0. (k_sl_wkey keeps its own loop — its rows follow an add, so nothing is
+// null at count >= 1 — because through a function it takes two more VGPRs: DESIGN.md §4.)
+__device__ __forceinline__ u32 slx_row_values(const KOut& ko, i64 cnt, u64 sum, u64 mn, u64 mx, u32 fl,
+                                              u64 (&w)[6 + SH_MAX_AGGS]) {
+    u32 nulls = 0;
+#pragma unroll
+    for (int o = 0; o < SH_MAX_AGGS; o++) {
+        w[5 + o] = 0;
+        if (o >= ko.n) continue;
+        const int src = ko.src[o];
+        u64 v = 0;
+        bool nul = false;
+        if (src == 0) v = (u64)cnt;
+        else if (src == 1) { nul = cnt == 0; v = sum; }
+        else if (src == 2) {
+            nul = cnt == 0;
+            if (!nul) v = (u64)__double_as_longlong(__longlong_as_double((i64)sum) / (double)cnt);
+        } else if (src == 3) { nul = (fl & 1u) == 0; v = mn; }
+        else { nul = (fl & 2u) == 0; v = mx; }
+        w[5 + o] = nul ? 0 : v;
+        nulls |= (nul ? 1u : 0u) << o;
+    }
+    return nulls;
+}
+
+template <bool HSUM, bool HMIN, bool HMAX>
+__global__ __launch_bounds__(64) SH_XW_ATTR void k_slx_wkey(const u32* __restrict__ key_off, u32 nslots,
+                                                const u32* __restrict__ sorted_rank, const u64* __restrict__ xa,
+                                                const u64* __restrict__ xx, i64 n_u, i64 X0, i64 G0, i64 seq_base,
+                                                i64 send_size, SlState S, i64* __restrict__ rg, DFields fd, KOut ko,
+                                                int cur_on, int exp_on, SlxRows rows,
+                                                unsigned char* __restrict__ flags) {
+    __shared__ u64 dq_min[HMIN ? kDqK : 1];
+    __shared__ u64 dq_max[HMAX ? kDqK : 1];
+    __shared__ int di_min[HMIN ? kDqK : 1];
+    __shared__ int di_max[HMAX ? kDqK : 1];
+    __shared__ u64 s_aop[64], s_ax[64], s_xop[64], s_xx[64], s_val[64];
+    __shared__ u64 s_pbn[HMIN ? 64 : 1], s_pbx[HMAX ? 64 : 1];
+    __shared__ int s_sel[64];
+    __shared__ u32 s_bf[kBfWords];
+    const u32 k = blockIdx.x;
+    const int lane = threadIdx.x;
+    if (k >= nslots) return;
+    const u32 lo = key_off[k];
+    const int A = (int)(key_off[k + 1] - lo);
+    const int H0 = (int)S.rlen[k];
+    if (A == 0 && H0 == 0) return;
+    const int gm = (int)(S.rc - 1);
+    const int rh0 = (int)(S.rhead[k] & gm);
+    const size_t kr = (size_t)k * S.rc;
+    const int HN = H0 + A;
+    WkState w{};
+    bool par = wk_load<HSUM, HMIN, HMAX>(w, S, fd, k, rh0, H0, dq_min, dq_max, di_min, di_max, s_bf, lane);
+    // (the running state under the names the replay uses)
+    i64& cnt = w.cnt;
+    double& sum = w.sum;
+    KDq &qn = w.qn, &qx = w.qx;
+    const u64 le = (2ull << lane) - 1ull;  // lanes <= this one (lane 63: all)
+    int ia = 0, ie = 0;                    // adds / FIFO entries consumed
+    i64 row_ch = -1, row_op = 0;           // the (chunk, key) row open at the chunk start
+    // the staged adds / FIFO entries: lane l holds add ia + l and entry ie + l; after a chunk the
+    // unconsumed ones move down (shuffles) and only the freed lanes load (each record read once)
+    u64 a_op = kNoOp, a_x = 0, a_ts = 0, a_clk = 0, a_ch = 0, a_rep = 0;
+    u64 x_op = kNoOp, x_x = 0, x_ts = 0, x_clk = 0, x_ch = 0, x_rep = 0;
+    int a_keep = 0, x_keep = 0;  // lanes still holding a staged operation
+    for (;;) {
+        // ---- stage up to the next 64 adds and the next 64 FIFO entries: one 48-byte record each (xa
+        // by record, xx by window position), the row fields kept in the staging lane's registers
+        if (lane >= a_keep) {
+            a_op = kNoOp;
+            a_x = a_ts = a_clk = a_ch = a_rep = 0;
+        }
+        if (lane >= x_keep) {
+            x_op = kNoOp;
+            x_x = x_ts = x_clk = x_ch = x_rep = 0;
+        }
+        if (lane >= a_keep && ia + lane < A) {
+            const u32 ar = sorted_rank[lo + (u32)(ia + lane)];
+            const ulonglong2* q = (const ulonglong2*)(xa + (size_t)ar * kXaWords);
+            const ulonglong2 w0 = q[0], w1 = q[1], w2 = q[2];
+            a_op = w0.x;
+            a_x = w0.y;
+            a_ts = w1.x;
+            a_clk = w1.y;
+            a_ch = 2 * (send_size > 0 ? w2.x / (u64)send_size : 0) + 1;
+            a_rep = (u64)seq_base + w2.x;
+        }
+        const int p = ie + lane;
+        if (lane >= x_keep && p < HN) {
+            i64 x_u;
+            if (p < H0) {
+                const size_t sl = kr + (size_t)((rh0 + p) & gm);
+                x_u = rg[sl] - X0;
+                x_x = S.rval[sl];
+            } else {
+                x_u = G0 + (i64)sorted_rank[lo + (u32)(p - H0)] - X0;
+            }
+            if (x_u >= 0 && x_u < n_u) {
+                const ulonglong2* q = (const ulonglong2*)(xx + (size_t)x_u * kXaWords);
+                const ulonglong2 w0 = q[0], w1 = q[1], w2 = q[2];
+                x_op = w0.x;
+                if (p >= H0) x_x = w0.y;
+                x_ts = w1.x;
+                x_clk = w1.y;
+                x_rep = w2.x;
+                x_ch = w2.y;
+            }
+        }
+        if (!__any(a_op != kNoOp || x_op != kNoOp)) break;
+        s_aop[lane] = a_op;
+        s_ax[lane] = a_x;
+        s_xop[lane] = x_op;
+        s_xx[lane] = x_x;
+        __syncthreads();
+        // ---- places in the merged order (both lists ascend; kNoOp pads the ends)
+        int pa = 64, px = 64;
+        if (a_op != kNoOp) {
+            int l2 = 0, h2 = 64;
+            while (l2 < h2) {
+                const int mid = (l2 + h2) >> 1;
+                if (s_xop[mid] < a_op) l2 = mid + 1;
+                else h2 = mid;
+            }
+            pa = lane + l2;
+        }
+        if (x_op != kNoOp) {
+            int l2 = 0, h2 = 64;
+            while (l2 < h2) {
+                const int mid = (l2 + h2) >> 1;
+                if (s_aop[mid] < x_op) l2 = mid + 1;
+                else h2 = mid;
+            }
+            px = lane + l2;
+        }
+        if (pa < 64) s_sel[pa] = lane;
+        if (px < 64) s_sel[px] = 64 | lane;
+        const int na_c = __popcll(__ballot(pa < 64)), nx_c = __popcll(__ballot(px < 64));
+        const int m = na_c + nx_c;
+        __syncthreads();
+        // ---- this lane's operation
+        const bool in = lane < m;
+        const int sel = in ? s_sel[lane] : 0;
+        const bool is_add = in && !(sel & 64);
+        const int si = sel & 63;
+        const u64 op = in ? (is_add ? s_aop[si] : s_xop[si]) : 0;
+        const u64 val = is_add ? s_ax[si] : s_xx[si];
+        // (every lane runs every shuffle)
+        const u64 sa_ts = shfl64(a_ts, si), sa_clk = shfl64(a_clk, si), sa_ch = shfl64(a_ch, si),
+                  sa_rep = shfl64(a_rep, si);
+        const u64 sx_ts = shfl64(x_ts, si), sx_clk = shfl64(x_clk, si), sx_ch = shfl64(x_ch, si),
+                  sx_rep = shfl64(x_rep, si);
+        const u64 am = __ballot(is_add), xm = __ballot(in && !is_add);
+        const int adds_le = __popcll(am & le), rems_le = __popcll(xm & le);
+        i64 r_cnt = cnt + adds_le - rems_le;
+        const int S0 = H0 + ia;        // window index of the chunk's first add
+        const int h_t = ie + rems_le;  // window head after this operation
+        const int h_end = ie + nx_c;
+        u64 r_sum = 0, r_mn = 0, r_mx = 0;
+        u32 r_fl = 0;
+        bool pc = par;
+        if (pc) {
+            // min / max in parallel: no NaN, no expiring value meeting a bit-equal one of another event
+            const bool ain = lane < na_c;  // add-space lane c = add ia + c (its staged lane)
+            pc = !__any(ain && d_isnan(a_x));
+            if (pc) {
+                bool dirty = false;
+                const u32 hx = bf_hash(a_x);
+                if (ain) atomicOr(&s_bf[hx >> 5], 1u << (hx & 31));
+                __syncthreads();
+                if (lane < nx_c) {
+                    const int idx = ie + lane;
+                    const u64 v = x_x;
+                    if (HMIN) dirty |= dq_quirk(qn, dq_min, di_min, v, idx);
+                    if (HMAX) dirty |= dq_quirk(qx, dq_max, di_max, v, idx);
+                    if (bf_hit(s_bf, v))
+                        for (int c = 0; c < na_c; c++) dirty |= s_ax[c] == v && S0 + c != idx;
+                }
+                __syncthreads();
+                if (ain) s_bf[hx >> 5] = 0;  // (after every lane's test)
+                pc = !__any(dirty);
+            }
+            DqPlan pn{}, px_{};
+            bool sn = false, sx = false;
+            if (pc) {
+                const bool from0 = h_end <= S0;  // no add of the chunk leaves within it
+                if (from0) {
+                    // leftmost-best prefix of the chunk's adds
+                    u64 bn = a_x, bx = a_x;
+#pragma unroll
+                    for (int d = 1; d < 64; d <<= 1) {
+                        const int src = lane >= d ? lane - d : lane;
+                        const u64 on = shfl64(bn, src), ox = shfl64(bx, src);
+                        if (lane >= d) {
+                            if (!d_worse<true>(on, bn)) bn = on;
+                            if (!d_worse<false>(ox, bx)) bx = ox;
+                        }
+                    }
+                    if (HMIN) s_pbn[lane] = bn;
+                    if (HMAX) s_pbx[lane] = bx;
+                }
+                __syncthreads();
+                if (in) {
+                    const int c0 = h_t - S0 > 0 ? h_t - S0 : 0;
+                    auto best = [&](const KDq& q, const u64* dv, const int* di, const u64* pb, bool MINB) -> u64 {
+                        int a = 0, b = q.len;
+                        while (a < b) {
+                            const int mid = (a + b) >> 1;
+                            if (di[(q.h + mid) & (kDqK - 1)] < h_t) a = mid + 1;
+                            else b = mid;
+                        }
+                        u64 bv = a < q.len ? dv[(q.h + a) & (kDqK - 1)] : 0;
+                        bool bh = a < q.len;
+                        u64 cv = 0;
+                        bool chh = false;
+                        if (from0) {
+                            if (adds_le > 0) { cv = pb[adds_le - 1]; chh = true; }
+                        } else {
+                            for (int c = c0; c < adds_le; c++) {
+                                const u64 v = s_ax[c];
+                                if (!chh || (MINB ? d_worse<true>(cv, v) : d_worse<false>(cv, v))) { cv = v; chh = true; }
+                            }
+                        }
+                        if (chh && (!bh || (MINB ? d_worse<true>(bv, cv) : d_worse<false>(bv, cv)))) bv = cv;
+                        return bv;
+                    };
+                    if (HMIN) r_mn = best(qn, dq_min, di_min, s_pbn, true);
+                    if (HMAX) r_mx = best(qx, dq_max, di_max, s_pbx, false);
+                    r_fl = r_cnt > 0 ? 3u : 0u;
+                }
+                if (HMIN) pn = dq_plan<true>(qn, dq_min, di_min, a_x, ain, S0, h_end, lane, sn);
+                if (HMAX) px_ = dq_plan<false>(qx, dq_max, di_max, a_x, ain, S0, h_end, lane, sx);
+                pc = (!HMIN || pn.i1 - pn.i0 + pn.n_new <= kDqK) && (!HMAX || px_.i1 - px_.i0 + px_.n_new <= kDqK);
+            }
+            if (pc) {
+                const bool live = cnt + na_c - nx_c > 0;
+                if (HMIN) {
+                    dq_commit<true>(qn, dq_min, di_min, pn, a_x, sn, S0, lane, rl64(r_mn, m - 1));
+                    qn.mmh = live && qn.len > 0;
+                }
+                if (HMAX) {
+                    dq_commit<false>(qx, dq_max, di_max, px_, a_x, sx, S0, lane, rl64(r_mx, m - 1));
+                    qx.mmh = live && qx.len > 0;
+                }
+            } else {
+                par = false;  // the sequential deque takes over for the rest of the push
+            }
+        }
+        if (pc || (!HMIN && !HMAX)) {
+            // the sum as one operation list: adds, negated removes, restarts where the count reaches 0
+            if (HSUM) {
+                if (in) s_val[lane] = is_add ? val : val ^ 0x8000000000000000ull;
+                const u64 czm[1] = {__ballot(in && !is_add && r_cnt == 0)};
+                __syncthreads();
+                r_sum = wk_sum_chain(sum, s_val, m, czm, lane);
+            }
+            cnt += na_c - nx_c;
+        } else {
+            // sequential: every operation in order on wave-uniform state
+            if (in) s_val[lane] = val;
+            __syncthreads();
+            for (int j = 0; j < m; j++) {
+                if (!(s_sel[j] & 64)) wk_add<HSUM, HMIN, HMAX>(w, dq_min, dq_max, s_val[j], true);
+                else wk_remove<HSUM, HMIN, HMAX>(w, dq_min, dq_max, s_val[j], true);
+                if (lane == j) {
+                    r_sum = (u64)__double_as_longlong(sum);
+                    r_mn = qn.mm;
+                    r_mx = qx.mm;
+                    r_fl = (qn.mmh ? 1u : 0u) | (qx.mmh ? 2u : 0u);
+                }
+            }
+        }
+        ia += na_c;
+        ie += nx_c;
+        {
+            // the unconsumed staged operations move down to lane 0 (every lane runs every shuffle)
+            const int sa = lane + na_c < 64 ? lane + na_c : 63, sx_ = lane + nx_c < 64 ? lane + nx_c : 63;
+            a_op = shfl64(a_op, sa);
+            a_x = shfl64(a_x, sa);
+            a_ts = shfl64(a_ts, sa);
+            a_clk = shfl64(a_clk, sa);
+            a_ch = shfl64(a_ch, sa);
+            a_rep = shfl64(a_rep, sa);
+            x_op = shfl64(x_op, sx_);
+            x_x = shfl64(x_x, sx_);
+            x_ts = shfl64(x_ts, sx_);
+            x_clk = shfl64(x_clk, sx_);
+            x_ch = shfl64(x_ch, sx_);
+            x_rep = shfl64(x_rep, sx_);
+            a_keep = 64 - na_c;
+            x_keep = 64 - nx_c;
+        }
+        // ---- rows: lanes segmented by their chunk among the qualifying operations
+        const i64 ch = in ? (i64)(is_add ? sa_ch : sx_ch) : 0;
+        const bool qual = in && (is_add ? cur_on : exp_on);
+        const u64 qm = __ballot(qual);
+        const u64 qb = qm & (le >> 1);  // qualifying lanes before this one
+        const int pl = qb ? 63 - __clzll(qb) : lane;
+        const i64 pch = (i64)shfl64((u64)ch, pl);
+        const i64 prev_ch = qb ? pch : row_ch;
+        const bool start = qual && ch != prev_ch;
+        if (start) flags[op] = 1;
+        const u64 stm = __ballot(start) & le;
+        const int sl = stm ? 63 - __clzll(stm) : lane;
+        const u64 sop = shfl64(op, sl);
+        const i64 my_row = stm ? (i64)sop : row_op;
+        const u64 qa = qm & ~le;  // qualifying lanes after this one
+        const int nl = qa ? __ffsll((long long)qa) - 1 : lane;
+        const i64 nch = (i64)shfl64((u64)ch, nl);
+        const bool end = qual && (!qa || nch != ch);
+        if (end) {
+            const i64 ts = (i64)(is_add ? sa_ts : sx_ts), rep = (i64)(is_add ? sa_rep : sx_rep),
+                      clk = (i64)(is_add ? sa_clk : sx_clk);
+            u64 row[6 + SH_MAX_AGGS];
+            row[0] = (u64)ts;
+            row[1] = (u64)rep;
+            row[2] = (u64)ch;
+            row[3] = (u64)clk;
+            const u64 nulls = slx_row_values(ko, r_cnt, r_sum, r_mn, r_mx, r_fl, row);
+            row[4] = (u64)k | ((u64)(is_add ? 0 : 1) << 32) | (nulls << 40);
+            ulonglong2* dst = (ulonglong2*)(rows.aos + (size_t)my_row * rows.rw);
+#pragma unroll
+            for (int o = 0; o < (6 + SH_MAX_AGGS) / 2; o++)
+                if (2 * o < rows.rw) dst[o] = make_ulonglong2(row[2 * o], row[2 * o + 1]);
+        }
+        if (qm) {  // (wave-uniform)
+            const int lq = 63 - __clzll(qm);
+            row_ch = (i64)shfl64((u64)ch, lq);
+            row_op = (i64)shfl64((u64)my_row, lq);
+        }
+        __syncthreads();  // the staging arrays are refilled by the next chunk
+    }
+    // ---- the window after the push: FIFO [ie, HN) (the push's records with their arrival index)
+    wk_write_back<HSUM, HMIN, HMAX>(w, S, fd, k, rh0, H0, HN, ie, dq_min, dq_max, lane, [&](size_t sl, int j) {
+        const u32 r = sorted_rank[lo + (u32)j];
+        const u64* q = xa + (size_t)r * kXaWords;
+        S.rpm[sl] = (i64)q[5];
+        S.rval[sl] = q[1];
+        rg[sl] = G0 + (i64)r;
+    });
+}
+
+// emission from the row records: flagged operation indices in order, each row read as one record
+__global__ __launch_bounds__(kBlock) void k_slx_emit_aos(const unsigned char* __restrict__ flags, i64 n,
+                                                        const i64* __restrict__ blk_pre, const u64* __restrict__ rows,
+                                                        int rw, int n_aggs, KeyTable kt, KeyPlan kp, i64 out_cap,
+                                                        i64* out_ts, i64* out_keys, u64* out_vals,
+                                                        unsigned char* out_nulls, unsigned char* out_exp, i64* out_ch,
+                                                        i64* out_clock, i64* out_rep) {
+    const i64 tile = (i64)blockIdx.x * kTile;
+    i64 run = blk_pre[blockIdx.x];
+    for (int it = 0; it < kItems; it++) {
+        const i64 j = tile + (i64)it * kBlock + threadIdx.x;
+        const i64 fl = j < n ? flags[j] : 0;
+        i64 tot;
+        const i64 r = run + block_excl_scan(fl, SumOp(), 0, &tot);
+        run += tot;
+        if (!fl) continue;
+        const ulonglong2* src = (const ulonglong2*)(rows + (size_t)j * rw);
+        const ulonglong2 a0 = src[0], a1 = src[1], a2 = src[2];
+        out_ts[r] = (i64)a0.x;
+        out_rep[r] = (i64)a0.y;
+        out_ch[r] = (i64)a1.x;
+        out_clock[r] = (i64)a1.y;
+        const u64 meta = a2.x;
+        unpack_key(kp, slot_key(kt, (u32)meta), out_keys + r, out_cap);
+        out_exp[r] = (unsigned char)((meta >> 32) & 1);
+        for (int a = 0; a < n_aggs; a++) {
+            out_vals[(size_t)a * out_cap + r] = a == 0 ? a2.y : rows[(size_t)j * rw + 5 + a];
+            out_nulls[(size_t)a * out_cap + r] = (unsigned char)((meta >> (40 + a)) & 1);
+        }
+    }
+}
+
+void launch_slx_emit_aos(hipStream_t s, const unsigned char* flags, i64 n, const i64* blk_pre, int nblk, SlxRows rows,
+                         int n_aggs, KeyTable kt, KeyPlan kp, i64 out_cap, i64* out_ts, i64* out_keys, u64* out_vals,
+                         unsigned char* out_nulls, unsigned char* out_exp, i64* out_ch, i64* out_clock, i64* out_rep) {
+    if (nblk <= 0) return;
+    hipLaunchKernelGGL(k_slx_emit_aos, dim3(nblk), dim3(kBlock), 0, s, flags, n, blk_pre, rows.aos, rows.rw, n_aggs, kt,
+                       kp, out_cap, out_ts, out_keys, out_vals, out_nulls, out_exp, out_ch, out_clock, out_rep);
+}
+
+bool slx_keyed_ok(AggPlan ap) {
+    DFields fd;
+    return own_d_fields(ap, fd) && ap.n <= SH_MAX_AGGS;
+}
+
+void launch_slx_wkey(hipStream_t s, const u32* key_off, const u32* sorted_rank, i64 nslots, const u64* xa,
+                     const u64* xx, i64 n_u, i64 X0, i64 G0, i64 seq_base, i64 send_size, SlState S, i64* rg,
+                     AggPlan ap, int cur_on, int exp_on, SlxRows rows, unsigned char* flags) {
+    if (nslots <= 0) return;
+    DFields fd;
+    own_d_fields(ap, fd);
+    const KOut ko = agg_outputs(ap);
+    for_agg_shape(fd, [&](auto HS, auto HN, auto HX) {
+        hipLaunchKernelGGL((k_slx_wkey<HS.value, HN.value, HX.value>), dim3((unsigned)nslots), dim3(64), 0, s, key_off,
+                           (u32)nslots, sorted_rank, xa, xx, n_u, X0, G0, seq_base, send_size, S, rg, fd, ko, cur_on,
+                           exp_on, rows, flags);
+    });
 }
 
 }  // namespace shd
