@@ -241,9 +241,26 @@ void launch_aggregate(hipStream_t s, const Segment* segs, int nseg, int P, int l
                       bool persistent = true);
 void launch_count_flags(hipStream_t s, const unsigned char* flags, i64 n, i64* blk_cnt, int nblk);
 void launch_scan_sum(hipStream_t s, i64* a, int n);
+// What a two-stream push's host reads after its final synchronisation, stored by k_bits_pre into
+// pinned host memory the device has mapped (no copy is queued behind the emission): seg_rank[2 i],
+// [2 i + 1] = the bitmap's rank (set bits below) at segs[i].lo and .hi — their difference is the
+// segment's row count — and the key table's four control words. seg_rank == nullptr: nothing stored.
+// zero_info (zero_words 32-bit words) and zero_tail (8 bytes), when set, are this push's info block and
+// tile-count tail, dead by then: zeroed here for the next push, which then starts with k_boundaries.
+struct TailOut {
+    const Segment* segs;
+    int nseg;
+    u32* seg_rank;
+    const u32* ctrl;
+    u32* h_ctrl;
+    u32* zero_info;
+    int zero_words;
+    u32* zero_tail;
+};
 // word_pre[w] = exclusive popcount prefix of the first-occurrence bitmap before word w (low 32 bits)
 // with word w itself (high 32 bits); *total = the bitmap's popcount
-void launch_bits_prefix(hipStream_t s, const u32* bits, i64 nw, i64* tile_sum, u64* word_pre, u32* total);
+void launch_bits_prefix(hipStream_t s, const u32* bits, i64 nw, i64* tile_sum, u64* word_pre, u32* total,
+                        TailOut to = TailOut{});
 // rows: the aggregation units' regions; the row count (for the output columns' stride) is read on
 // the device (launch_bits_prefix's total); row_cap bounds it
 void launch_emit_rows(hipStream_t s, const u64* rows, int RW, const u32* unit_rows, i64 n_units, int unit_stride,

@@ -1114,7 +1114,7 @@ __global__ __launch_bounds__(kBlock) void k_bits_tile(const u32* __restrict__ bi
 }
 
 __global__ __launch_bounds__(kBlock) void k_bits_pre(const u32* __restrict__ bits, i64 nw, const i64* tile_pre,
-                                                    u64* word_pre, u32* total) {
+                                                    u64* word_pre, u32* total, TailOut to) {
     const i64 base = (i64)blockIdx.x * kTile + (i64)threadIdx.x * kItems;
     u32 b[kItems];
     i64 c = 0;
@@ -1127,13 +1127,44 @@ __global__ __launch_bounds__(kBlock) void k_bits_pre(const u32* __restrict__ bit
         r += __popc(b[i]);
         if (base + i == nw - 1) *total = (u32)r;  // every row's first event has one bit: the row count
     }
+    if (!to.seg_rank) return;
+    // the ranks at the segment ends that lie in this workgroup's words, from the words it just wrote,
+    // and the key table's control words (final since k_boundaries): plain stores to mapped host memory
+    __syncthreads();
+    // (the segments are sorted and do not overlap, so lo0, hi0, lo1, hi1, ... do not decrease: a binary
+    // search finds the first end at or behind this workgroup's first event, and the walk stops at the first
+    // one behind its last — a push that closes tens of thousands of windows costs each workgroup ~17 loads)
+    const i64 e_lo = (i64)blockIdx.x * kTile * 32, e_hi = min(nw, (i64)(blockIdx.x + 1) * kTile) * 32;
+    const int n_ends = 2 * to.nseg;
+    int first = 0;
+    for (int hi = n_ends; first < hi;) {
+        const int mid = (first + hi) >> 1;
+        const i64 e = mid & 1 ? to.segs[mid >> 1].hi : to.segs[mid >> 1].lo;
+        if (e < e_lo) first = mid + 1;
+        else hi = mid;
+    }
+    for (int i = first + threadIdx.x; i < n_ends; i += kBlock) {
+        const i64 e = i & 1 ? to.segs[i >> 1].hi : to.segs[i >> 1].lo;
+        if (e >= e_hi) break;
+        const i64 w = e >> 5;
+        const u64 wp = __atomic_load_n(&word_pre[w], __ATOMIC_RELAXED);
+        to.seg_rank[i] = (u32)wp + (u32)__popc((u32)(wp >> 32) & ((1u << (e & 31)) - 1u));
+    }
+    if (blockIdx.x != 0) return;
+    if (threadIdx.x < 4) to.h_ctrl[threadIdx.x] = to.ctrl[threadIdx.x];
+    // (k_compact_pending, which may still run on the side stream, reads only the tile prefixes below nblk,
+    // never the tile-count tail or the info block, and nothing reads the info block after the host's copy)
+    if (to.zero_info) {
+        for (int i = threadIdx.x; i < to.zero_words; i += kBlock) to.zero_info[i] = 0;
+        if (threadIdx.x < 2) to.zero_tail[threadIdx.x] = 0;
+    }
 }
 
-void launch_bits_prefix(hipStream_t s, const u32* bits, i64 nw, i64* tile_sum, u64* word_pre, u32* total) {
+void launch_bits_prefix(hipStream_t s, const u32* bits, i64 nw, i64* tile_sum, u64* word_pre, u32* total, TailOut to) {
     const int nb = (int)((nw + kTile - 1) / kTile);
     hipLaunchKernelGGL(k_bits_tile, dim3(nb), dim3(kBlock), 0, s, bits, nw, tile_sum);
     launch_scan_sum(s, tile_sum, nb);
-    hipLaunchKernelGGL(k_bits_pre, dim3(nb), dim3(kBlock), 0, s, bits, nw, tile_sum, word_pre, total);
+    hipLaunchKernelGGL(k_bits_pre, dim3(nb), dim3(kBlock), 0, s, bits, nw, tile_sum, word_pre, total, to);
 }
 
 // Output rows are staged as records of stage_words(nk, na, order) u64 words at their output
@@ -1727,58 +1758,126 @@ void launch_part_off(hipStream_t s, const i64* counts, int nblk, int P, i64* par
 // (partition-major, tile order inside a partition). Row nblk gets each partition's end. Three passes
 // over coalesced rows: per block of kColT tiles the per-partition sums, per partition the exclusive
 // scan over the blocks (+ its total), the scan of the totals over the partitions, then the rows.
+// A thread's kColT rows are loaded before any of them is used (reduce) or overwritten (apply): one
+// round trip to memory instead of kColT dependent ones.
 constexpr int kColT = 16;
 __global__ __launch_bounds__(kBlock) void k_col_reduce(const u32* __restrict__ c, int nblk, int P, i64* bsum,
                                                       u32* ticket) {
     const int b = blockIdx.y;
     const int p = blockIdx.x * kBlock + threadIdx.x;
-    if (b == 0 && p == 0) *ticket = 0;  // k_col_blocks' completion count
+    if (b == 0 && p == 0) *ticket = 0;  // k_col_lines' completion count
     if (p >= P) return;
     const int t0 = b * kColT, t1 = min(nblk, t0 + kColT);
+    u32 x[kColT];
+#pragma unroll
+    for (int k = 0; k < kColT; k++) x[k] = t0 + k < t1 ? c[(i64)(t0 + k) * P + p] : 0u;
     i64 acc = 0;
-    for (int t = t0; t < t1; t++) acc += c[(i64)t * P + p];
+#pragma unroll
+    for (int k = 0; k < kColT; k++) acc += x[k];
     bsum[(i64)b * P + p] = acc;
 }
 
-// One workgroup per partition: the exclusive scan of its column of block sums, kBlock blocks at a
-// time (a thread per column walking every block serialised nb dependent loads: 63 us at C2 size).
-// The last workgroup to finish also turns the partitions' totals into their bases (an exclusive scan
-// over P), so no separate copy + scan launches.
-__global__ __launch_bounds__(kBlock) void k_col_blocks(i64* bsum, int nb, int P, i64* total, i64* base, u32* ticket) {
-    const int p = blockIdx.x;
-    i64 run = 0;
-    for (int b0 = 0; b0 < nb; b0 += kBlock) {
-        const int b = b0 + threadIdx.x;
-        const i64 x = b < nb ? bsum[(i64)b * P + p] : 0;
-        i64 tot;
-        const i64 pre = block_excl_scan(x, SumOp(), 0, &tot);
-        if (b < nb) bsum[(i64)b * P + p] = run + pre;
-        run += tot;
-    }
+// The exclusive scan of every partition's column of block sums (+ the column's total). bsum is
+// [block][P]: a workgroup takes one 128-byte line of partitions (kLineP of them, or all P when there
+// are fewer) and G = kLineT / kLineP groups of consecutive block rows, so every load and store of a
+// wave covers whole lines (a workgroup per partition touched a line per 8-byte word: 17 MB read and
+// 8.5 MB written for 1 MB of block sums at C2 size, 19.8 us). Each thread sums its rows, the groups'
+// sums are prefixed through LDS, then the rows are replaced by their prefixes. The last workgroup to
+// finish also turns the partitions' totals into their bases (an exclusive scan over P), so no
+// separate copy + scan launches.
+constexpr int kLineT = 1024, kLineP = 16, kLineU = 8, kLineKeep = 24;
+__global__ __launch_bounds__(kLineT) void k_col_lines(i64* bsum, int nb, int P, i64* total, i64* base, u32* ticket) {
+    __shared__ i64 gsum[kLineT];  // [group][partition of the line]: a thread's own index
     __shared__ bool last;
-    if (threadIdx.x == 0) {
+    const int t = threadIdx.x;
+    const int lw = min(P, kLineP), G = kLineT / lw;  // (P is a power of two: so is lw)
+    const int l = t & (lw - 1), g = t / lw;
+    const int p = blockIdx.x * lw + l;
+    const int rpt = (nb + G - 1) / G;
+    const int r0 = min(nb, g * rpt), r1 = min(nb, r0 + rpt);
+    i64* const col = bsum + p;
+    // up to kLineKeep rows per thread (1,536 block rows, 50 M events) stay in registers: one round trip
+    // (as u32: a block sum counts events of kColT tiles)
+    const bool keep = rpt <= kLineKeep;
+    u32 x[kLineKeep];
+    i64 acc = 0;
+    if (keep) {
+#pragma unroll
+        for (int k = 0; k < kLineKeep; k++) x[k] = r0 + k < r1 ? (u32)col[(i64)(r0 + k) * P] : 0u;
+#pragma unroll
+        for (int k = 0; k < kLineKeep; k++) acc += x[k];
+    } else {
+        for (int r = r0; r < r1; r += kLineU) {
+            i64 y[kLineU];
+#pragma unroll
+            for (int k = 0; k < kLineU; k++) y[k] = r + k < r1 ? col[(i64)(r + k) * P] : 0;
+#pragma unroll
+            for (int k = 0; k < kLineU; k++) acc += y[k];
+        }
+    }
+    gsum[t] = acc;
+    __syncthreads();
+    // the groups before this one, for the thread's partition: up to 64 groups (a whole line of partitions)
+    // are added up one by one; fewer partitions mean up to 1,024 groups (P = 1: 36 us in that loop), which
+    // take a doubling ladder over the threads at the same place of a group instead
+    i64 run = 0;
+    if (G <= 64) {
+        for (int k = 0; k < g; k++) run += gsum[k * lw + l];
+    } else {
+        for (int d = lw; d < kLineT; d <<= 1) {
+            const i64 v = t >= d ? gsum[t - d] : 0;
+            __syncthreads();
+            gsum[t] += v;
+            __syncthreads();
+        }
+        run = gsum[t] - acc;
+    }
+    if (keep) {
+#pragma unroll
+        for (int k = 0; k < kLineKeep; k++) {
+            if (r0 + k < r1) col[(i64)(r0 + k) * P] = run;
+            run += x[k];
+        }
+    } else {
+        for (int r = r0; r < r1; r += kLineU) {  // (read again: cache hits)
+            i64 y[kLineU];
+#pragma unroll
+            for (int k = 0; k < kLineU; k++) y[k] = r + k < r1 ? col[(i64)(r + k) * P] : 0;
+#pragma unroll
+            for (int k = 0; k < kLineU; k++) {
+                if (r + k < r1) col[(i64)(r + k) * P] = run;
+                run += y[k];
+            }
+        }
+    }
+    if (g == G - 1) {  // (the last group ends at row nb: its running sum is the column's total)
         total[p] = run;
         __threadfence();
-        last = atomicAdd(ticket, 1u) == (u32)(P - 1);
+    }
+    __syncthreads();
+    if (t == 0) {
+        last = atomicAdd(ticket, 1u) == gridDim.x - 1;
+        if (last) __threadfence();  // (one acquire for the workgroup, in front of the barrier; the loads below bypass L1)
     }
     __syncthreads();
     if (!last) return;
-    __threadfence();
-    i64 carry = 0;
-    for (int q0 = 0; q0 < P; q0 += kBlock) {
-        const int q = q0 + threadIdx.x;
-        const i64 x = q < P ? __atomic_load_n(&total[q], __ATOMIC_RELAXED) : 0;
-        i64 tot;
-        const i64 pre = block_excl_scan(x, SumOp(), 0, &tot);
-        if (q < P) base[q] = carry + pre;
-        carry += tot;
+    // the totals' exclusive scan: a thread's run of consecutive partitions, then the threads' sums
+    const int per = (P + kLineT - 1) / kLineT;
+    const int q0 = min(P, t * per), q1 = min(P, q0 + per);
+    i64 mine = 0;
+    for (int q = q0; q < q1; q++) mine += __atomic_load_n(&total[q], __ATOMIC_RELAXED);
+    i64 pre = block_excl_scan_any(mine, nullptr);
+    for (int q = q0; q < q1; q++) {
+        base[q] = pre;
+        pre += __atomic_load_n(&total[q], __ATOMIC_RELAXED);
     }
 }
 
 // Many partitions over few block rows (C4's band-keyed roots: 16k partitions, ~64 rows): a thread per
 // partition walks its column (coalesced across the partitions; the rows are loaded 8 at a time) and
-// the partitions' totals are scanned by k_scan_sum — k_col_blocks' one workgroup per partition plus
-// its last workgroup's P / kBlock serial block scans cost ~95 us there.
+// the partitions' totals are scanned by k_scan_sum (one workgroup per partition plus its last
+// workgroup's P / kBlock serial block scans cost ~95 us there; k_col_lines would run P / 16
+// workgroups of mostly idle threads over so few rows).
 __global__ __launch_bounds__(kBlock) void k_col_walk(i64* __restrict__ bsum, int nb, int P, i64* __restrict__ total,
                                                     i64* __restrict__ base) {
     const int p = blockIdx.x * kBlock + threadIdx.x;
@@ -1805,10 +1904,13 @@ __global__ __launch_bounds__(kBlock) void k_col_apply(u32* c, int nblk, int P, c
     if (p >= P) return;
     const int t0 = b * kColT, t1 = min(nblk, t0 + kColT);
     i64 run = base[p] + bpre[(i64)b * P + p];
-    for (int t = t0; t < t1; t++) {
-        const u32 x = c[(i64)t * P + p];
-        c[(i64)t * P + p] = (u32)run;
-        run += x;
+    u32 x[kColT];
+#pragma unroll
+    for (int k = 0; k < kColT; k++) x[k] = t0 + k < t1 ? c[(i64)(t0 + k) * P + p] : 0u;
+#pragma unroll
+    for (int k = 0; k < kColT; k++) {
+        if (t0 + k < t1) c[(i64)(t0 + k) * P + p] = (u32)run;
+        run += x[k];
     }
     if (t1 == nblk) c[(i64)nblk * P + p] = (u32)(base[p] + total[p]);
 }
@@ -1831,7 +1933,7 @@ void launch_ms_offsets(hipStream_t s, u32* counts, int nblk, int P, i64* tmp) {
         hipLaunchKernelGGL(k_col_walk, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, bsum, nb, P, total, base);
         launch_scan_sum(s, base, P);
     } else {
-        hipLaunchKernelGGL(k_col_blocks, dim3(P), dim3(kBlock), 0, s, bsum, nb, P, total, base, ticket);
+        hipLaunchKernelGGL(k_col_lines, dim3(P / std::min(P, kLineP)), dim3(kLineT), 0, s, bsum, nb, P, total, base, ticket);
     }
     if (nblk > 0) hipLaunchKernelGGL(k_col_apply, g, dim3(kBlock), 0, s, counts, nblk, P, bsum, base, total);
     else hipLaunchKernelGGL(k_col_apply, dim3((P + kBlock - 1) / kBlock, 1), dim3(kBlock), 0, s, counts, nblk, P, bsum,

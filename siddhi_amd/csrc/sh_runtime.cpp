@@ -143,8 +143,10 @@ int PinnedBuf::reserve(size_t n) {
     if (n <= cap) return SH_OK;
     release();
     size_t ncap = std::max<size_t>(n, 4096);
-    if (hipHostMalloc(&p, ncap, hipHostMallocDefault) != hipSuccess) {
-        p = nullptr;
+    if (hipHostMalloc(&p, ncap, mapped ? hipHostMallocMapped | hipHostMallocCoherent : hipHostMallocDefault) != hipSuccess ||
+        (mapped && hipHostGetDevicePointer(&dev, p, 0) != hipSuccess)) {
+        if (p) (void)hipHostFree(p);
+        p = dev = nullptr;
         return sh_fail(SH_ERR_OOM, "pinned host allocation failed");
     }
     cap = ncap;
@@ -153,7 +155,7 @@ int PinnedBuf::reserve(size_t n) {
 
 void PinnedBuf::release() {
     if (p) (void)hipHostFree(p);
-    p = nullptr;
+    p = dev = nullptr;
     cap = 0;
 }
 

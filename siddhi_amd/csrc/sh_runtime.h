@@ -104,15 +104,23 @@ struct DevBuf {
 struct PinnedBuf {
     void* p = nullptr;
     size_t cap = 0;
+    // mapped: allocated hipHostMallocMapped | hipHostMallocCoherent for kernels that store into it; dev is
+    // the device's pointer to it, fetched with the allocation (set `mapped` before the first reserve)
+    bool mapped = false;
+    void* dev = nullptr;
     PinnedBuf() = default;
+    explicit PinnedBuf(bool device_mapped) : mapped(device_mapped) {}
     PinnedBuf(const PinnedBuf&) = delete;
     PinnedBuf& operator=(const PinnedBuf&) = delete;
-    PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), cap(o.cap), mapped(o.mapped), dev(o.dev) {
+        o.p = o.dev = nullptr;
+        o.cap = 0;
+    }
     PinnedBuf& operator=(PinnedBuf&& o) noexcept {
         if (this != &o) {
             release();
-            p = o.p; cap = o.cap;
-            o.p = nullptr; o.cap = 0;
+            p = o.p; cap = o.cap; mapped = o.mapped; dev = o.dev;
+            o.p = o.dev = nullptr; o.cap = 0;
         }
         return *this;
     }
@@ -342,7 +350,9 @@ struct sh_query {
     DevBuf new_pos, seg_off;  // key slot per event of the push (kNoPos = filtered out); segment record offsets
     PushInfo* h_info = nullptr;
     PinnedBuf h_up;    // pinned segment list of the closed windows (read by the kernels in place)
-    PinnedBuf h_tail;  // pinned landing area of the push's final copies: key-table counters, rows per segment
+    // pinned landing area of the push's final copies: key-table counters, rows per segment; device-mapped,
+    // since a two-stream push's k_bits_pre stores them there itself (TailOut)
+    PinnedBuf h_tail{true};
     PinnedBuf h_bounds;  // pinned landing area of the push's window boundaries
     // the multisplit of the push's events, launched before the host reads the window boundaries
     bool ms_ready = false;
@@ -379,6 +389,9 @@ struct sh_query {
     // flush bookkeeping of the closed windows, completed after the push's final synchronisation
     struct ClosedTail {
         bool active = false, host_done = false;
+        // a two-stream push: h_tail holds the bitmap's ranks at the segment ends (two per segment) instead
+        // of the rows per unit, and the key table's control words, all stored by k_bits_pre (TailOut)
+        bool seg_ranks = false;
         int nseg = 0, units_per_seg = 1;
         int64_t closed_hi = 0;
         std::vector<int64_t> clocks, windows;
@@ -395,6 +408,19 @@ struct sh_query {
     // side-stream ordering of a push: pending tiles counted (side), multisplit offsets scanned (main),
     // segment offsets and bitmap ready (side), open window compacted into the spare buffers (side)
     hipEvent_t ev_cnt = nullptr, ev_ms_off = nullptr, ev_seg = nullptr, ev_cmp = nullptr;
+    // The info block and the tile-count tail a single-pass push zeroes in front of k_boundaries (k_zero2).
+    // A two-stream push that closed windows has k_bits_pre zero them again once they are dead (TailOut) and,
+    // when it ends well, leaves them in head_clean; the next push skips k_zero2 if its own two regions are
+    // those. Every call clears head_clean first, so any other path and a failed push zero at the start.
+    struct HeadRegions {
+        void* info = nullptr;
+        void* tail = nullptr;
+        size_t info_cap = 0, tail_cap = 0;  // (the buffers' sizes: a regrown buffer may come back at the same address)
+        bool same(const HeadRegions& o) const {
+            return info && info == o.info && tail == o.tail && info_cap == o.info_cap && tail_cap == o.tail_cap;
+        }
+    } head_clean, head_want;
+    bool head_queued = false;  // run_closed handed head_want to k_bits_pre
     sh_stats stats{};
     int64_t agg_bytes = 0;
     // per flush of the last push: window number (internal use by the aggregation root)

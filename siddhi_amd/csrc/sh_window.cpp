@@ -458,9 +458,12 @@ static bool direct_pos_ok(const sh_query* q) {
 }
 
 static bool want_direct_pos(const sh_query* q) {
-    // opt-in (SH_DIRECT_POS=1) for the two-pass split: measured slower on MI355X — k_ms_scatter 290 vs
-    // 236 us per C2 push reading the key column instead of the slot column k_boundaries writes
-    // (profiles/r03_c2_v3*)
+    // opt-in (SH_DIRECT_POS=1) for the two-pass split: measured slower on MI355X, twice. Round 3: k_ms_scatter
+    // 290 vs 236 us per C2 push reading the key column instead of the slot column k_boundaries writes
+    // (profiles/r03_c2_v3*). Again on the two-stream push with the persistent fold: k_boundaries 143 -> 131 us
+    // but k_ms_scatter 226 -> 292 us, the push 0.965 against 0.919 ms (profiles/push_gaps_direct_pos_*).
+    // About a third of that is in the code: pos_at's clamp waits for its load inside every round of the
+    // scatter's load loop (273 us with the clamp behind the loop); the rest is unexplained
     return q->tune.direct_pos && direct_pos_ok(q);
 }
 
@@ -564,6 +567,7 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
         auto& t = q->tail;
         t.active = true;
         t.host_done = false;
+        t.seg_ranks = false;
         t.nseg = nseg;
         t.units_per_seg = 1;
         t.closed_hi = closed_hi;
@@ -649,8 +653,24 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
     RCHK(q->blk_cnt.reserve((nbt + 16) * 8, false));
     RCHK(q->word_pre.reserve((size_t)n_words * 8, false));
     if (!gather) RCHK(q->emit_stage.reserve(emit_stage_bytes(nk, na, q->given ? 1 : 0, cap), false));
+    // a two-stream push's tail: the rows per segment (as bitmap ranks) and the key table's control words
+    // are stored into h_tail by k_bits_pre, so no copy waits behind the emission (each was a blit kernel
+    // behind a 10-12 us gap). The other paths copy the rows per unit and the control words as before.
+    const bool tail_direct = side && gather;
+    RCHK(q->h_tail.reserve(16 + (size_t)std::max<int64_t>(n_units, 2 * (int64_t)nseg) * 4));
+    TailOut to{};
+    if (tail_direct) {
+        char* const d_tail = (char*)q->h_tail.dev;  // (h_tail is device-mapped: the pointer came with the allocation)
+        to = TailOut{dsegs, nseg, (u32*)(d_tail + 16), (const u32*)q->kt.ctrl.p, (u32*)d_tail, nullptr, 0, nullptr};
+        if (q->head_want.info) {
+            to.zero_info = (u32*)q->head_want.info;
+            to.zero_words = (int)(sizeof(PushInfo) / 4);
+            to.zero_tail = (u32*)q->head_want.tail;
+            q->head_queued = true;
+        }
+    }
     launch_bits_prefix(s, q->first_bits.as<u32>(), n_words, q->blk_cnt.as<int64_t>(), q->word_pre.as<u64>(),
-                       q->counters.as<u32>());
+                       q->counters.as<u32>(), to);
     if (gather)
         launch_emit_gather(s, q->word_pre.as<u64>(), n_words, dsegs, nseg, q->P, q->logP, unit_stride, q->rows.as<u64>(),
                            RW, pos_src(q, b), q->pend_pos.as<u32>(), q->n_pend, q->counters.as<u32>(), na, q->kt.dev(),
@@ -676,11 +696,11 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
     }
     HIPCHK(hipGetLastError());
     // rows per unit land in pinned memory with the push's final copies
-    RCHK(q->h_tail.reserve(16 + (size_t)n_units * 4));
-    HIPCHK(hipMemcpyAsync(q->h_tail.as<char>() + 16, unit_rows, n_units * 4, hipMemcpyDeviceToHost, s));
+    if (!tail_direct) HIPCHK(hipMemcpyAsync(q->h_tail.as<char>() + 16, unit_rows, n_units * 4, hipMemcpyDeviceToHost, s));
     auto& t = q->tail;
     t.active = true;
     t.host_done = false;
+    t.seg_ranks = tail_direct;
     t.nseg = nseg;
     t.units_per_seg = own ? q->P : 1;
     t.closed_hi = closed_hi;
@@ -702,8 +722,13 @@ static int closed_finish(sh_query* q, bool host_out) {
     hipStream_t s = q->ctx->stream;
     const uint32_t* unit_rows = (const uint32_t*)(q->h_tail.as<char>() + 16);
     std::vector<int64_t> seg_rows(t.nseg, 0);
-    for (int i = 0; i < t.nseg; i++)
+    for (int i = 0; i < t.nseg; i++) {
+        if (t.seg_ranks) {
+            seg_rows[i] = unit_rows[2 * i + 1] - unit_rows[2 * i];  // (ranks at the segment's hi and lo)
+            continue;
+        }
         for (int u = 0; u < t.units_per_seg; u++) seg_rows[i] += unit_rows[(size_t)i * t.units_per_seg + u];
+    }
     const int na = q->ap.n, nk = q->kp.n;
     int64_t n_rows = 0;
     for (int i = 0; i < t.nseg; i++) n_rows += seg_rows[i];
@@ -791,6 +816,10 @@ static void reset_call_output(sh_query* q) {
     q->ms_ready = false;
     q->side_push = false;
     q->tail.active = false;
+    q->tail.seg_ranks = false;
+    q->head_clean = {};
+    q->head_want = {};
+    q->head_queued = false;
 }
 
 // sh_query_set_device_flushes: a batch window's flush layout (built on the host: a few entries per
@@ -918,6 +947,7 @@ int query_resize_for_restore(sh_query* q, size_t table_size, int64_t n_pend, con
     }
     RCHK(size_partitions(q));
     q->n_pend = 0;
+    q->head_clean = {};
     return grow_pending(q, n_pend, 0);
 }
 
@@ -1300,6 +1330,7 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
     q->x_stamps.clear();
     hipStream_t s = q->ctx->stream;
     q->out.reset();
+    const sh_query::HeadRegions clean = q->head_clean;  // (what the last call left zeroed, if it was a push like this)
     reset_call_output(q);
     q->stats = sh_stats{};
     q->agg_bytes = 0;
@@ -1373,10 +1404,14 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
             launch_scan_blocks(s, q->blk_pass.as<int64_t>(), q->blk_tl.as<int64_t>(), q->blk_first.as<int64_t>(), nblk,
                                b->ts, wp, d_info, ext ? q->blk_xm.as<int64_t>() : nullptr, cs);
         };
+        sh_query::HeadRegions head;
         if (single_pass) {
             RCHK(q->blk_pass.reserve((size_t)(nblk + 1) * 8, false));
-            launch_zero2(s, d_info, (int)sizeof(PushInfo), q->blk_pass.as<int64_t>() + nblk, 8);
-            HIPCHK(hipGetLastError());
+            head = sh_query::HeadRegions{d_info, q->blk_pass.as<int64_t>() + nblk, q->bounds.cap, q->blk_pass.cap};
+            if (!head.same(clean)) {
+                launch_zero2(s, d_info, (int)sizeof(PushInfo), q->blk_pass.as<int64_t>() + nblk, 8);
+                HIPCHK(hipGetLastError());
+            }
         } else {
             prefix_passes();
         }
@@ -1393,6 +1428,7 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
         // sharded owner's given windows and externalTimeBatch timeouts (several run_closed calls per
         // push) keep the one stream.
         q->side_push = early_split && q->tune.side_stream && !q->hv.on && q->ap.n != 0 && !q->given && q->xt_timeout == 0;
+        if (q->side_push) q->head_want = head;  // (set for a single-pass push only)
         launch_boundaries(s, b->ts, cs, q->fp, wp, q->blk_pass.as<int64_t>(), q->blk_tl.as<int64_t>(),
                           d_info, d_bounds, max_bounds, nblk, q->kp, q->kt.dev(),
                           slot_col, ext ? q->blk_xm.as<int64_t>() : nullptr,
@@ -1409,10 +1445,10 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
         const size_t first_bytes = kInfoPad + (size_t)nb0 * sizeof(Bound);
         RCHK(q->h_bounds.reserve(first_bytes));
         const Bound* const h_bounds = (const Bound*)(q->h_bounds.as<char>() + kInfoPad);
-        HIPCHK(hipMemcpyAsync(q->h_bounds.p, q->bounds.p, first_bytes, hipMemcpyDeviceToHost, s));
         // stream.current over a hashed table packs (window, slot) sort keys (sc_rows): whether this push's
         // lookups handed out the reserved slot, mask + 1, comes back with the push info until it is known
         const bool rsv_probe = q->d.stream_current && !q->kt.dense && !q->kt.reserved_used;
+        HIPCHK(hipMemcpyAsync(q->h_bounds.p, q->bounds.p, first_bytes, hipMemcpyDeviceToHost, s));
         if (q->band_spec || rsv_probe) {
             // (a speculatively placed band: its overflow word comes back with the push info)
             RCHK(q->h_spec.reserve(16));
@@ -1603,8 +1639,9 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
     q->seq += N;
     HIPCHK(hipEventRecord(q->ev_push1, s));
     // the push's one final synchronisation: key-table counters and rows per segment
+    // (a two-stream push that closed windows: k_bits_pre has stored them there already)
     RCHK(q->h_tail.reserve(16));
-    RCHK(q->kt.check_async(s, q->h_tail.as<uint32_t>()));
+    if (!(q->tail.active && q->tail.seg_ranks)) RCHK(q->kt.check_async(s, q->h_tail.as<uint32_t>()));
     SH_TRACE("push final sync");
     SH_TMARK(4);
     HIPCHK(sh_wait_stream(s));
@@ -1622,6 +1659,7 @@ static int push_core(sh_query* q, const sh_batch* b, bool host_out_req, const sh
     q->stats.main_kernel_bytes = q->agg_bytes;
     if (q->xmode) return xout_finish(q, host_out_req, out);
     RCHK(finish_out(q, host_out, out));
+    if (q->head_queued) q->head_clean = q->head_want;
     SH_TMARK(6);
     return SH_OK;
 }
