@@ -213,6 +213,17 @@ __host__ __device__ inline i64 ev_seq(const EvSrc& es, u32 c) {
     return es.new_gidx ? (i64)es.new_gidx[c - es.n_pend] : es.seq_base + (i64)(c - es.n_pend);
 }
 
+// Where the fold marks a row's first event (combined index space). `flags` set: one byte per event, the
+// push's epoch (1..255) stored with a plain store — distinct bytes, published by the kernel boundary, and
+// a byte left by an earlier push holds another epoch, so nothing is cleared between pushes; the bitmap
+// words are then packed from the bytes (launch_bits_prefix). `flags` null: a device-scope atomicOr on
+// the bitmap word, which the caller has zeroed (SH_FIRST_FLAGS=0).
+struct FirstMarks {
+    u32* bits;
+    unsigned char* flags;
+    u32 epoch;
+};
+
 // Launchers (sh_kernels.hip).
 void launch_blockagg(hipStream_t s, const i64* ts, ColSet cols, FilterProg f, i64 N, i64 send_size,
                      i64* blk_pass, i64* blk_tl, i64* blk_first, int nblk, i64* blk_xm = nullptr, int ts_col = -1);
@@ -233,12 +244,14 @@ void launch_boundaries(hipStream_t s, const i64* ts, ColSet cols, FilterProg f, 
 int agg_unit_rows(int P, int NL, bool own);
 void launch_aggregate(hipStream_t s, const Segment* segs, int nseg, int P, int logP, int NL, i64 n_pend,
                       const u32* pend_pos, const u64* pend_vals, i64 pend_cap, const u32* new_pos, ColSet cols,
-                      AggPlan ap, u64* rows, int RW, u32* unit_rows, u32* first_bits,
+                      AggPlan ap, u64* rows, int RW, u32* unit_rows, FirstMarks marks,
                       // multisplit source (P > 1 or long windows; null: the flat kernel reads the batch)
                       const u32* rec_pos, const u32* rec_idx, const u64* rec_vals, i64 rec_cap, const i64* seg_off,
                       bool pack, EvSrc es, bool dense_rows = false,
                       // the multisplit kernel as a persistent grid with the next unit's records in flight
-                      bool persistent = true);
+                      bool persistent = true,
+                      // the persistent grid's workgroups of one XCD take one contiguous run of units
+                      bool xcd_units = true);
 void launch_count_flags(hipStream_t s, const unsigned char* flags, i64 n, i64* blk_cnt, int nblk);
 void launch_scan_sum(hipStream_t s, i64* a, int n);
 // What a two-stream push's host reads after its final synchronisation, stored by k_bits_pre into
@@ -258,8 +271,9 @@ struct TailOut {
     u32* zero_tail;
 };
 // word_pre[w] = exclusive popcount prefix of the first-occurrence bitmap before word w (low 32 bits)
-// with word w itself (high 32 bits); *total = the bitmap's popcount
-void launch_bits_prefix(hipStream_t s, const u32* bits, i64 nw, i64* tile_sum, u64* word_pre, u32* total,
+// with word w itself (high 32 bits); *total = the bitmap's popcount. With marks.flags the bitmap's words
+// are first packed from the flag bytes that hold marks.epoch (nw * 32 bytes are read).
+void launch_bits_prefix(hipStream_t s, FirstMarks marks, i64 nw, i64* tile_sum, u64* word_pre, u32* total,
                         TailOut to = TailOut{});
 // rows: the aggregation units' regions; the row count (for the output columns' stride) is read on
 // the device (launch_bits_prefix's total); row_cap bounds it

@@ -240,6 +240,11 @@ Tuning Tuning::from_env() {
     t.side_stream = !getenv("SH_SIDE_STREAM") || on("SH_SIDE_STREAM");
     // the multisplit fold as a persistent grid; =0 puts back one workgroup per unit, for A/B runs and bisecting
     t.fold_grid = !getenv("SH_FOLD_GRID") || on("SH_FOLD_GRID");
+    // first-occurrence marks as epoch bytes (chosen per push unless set), and an XCD-contiguous run of the
+    // persistent fold's units; =0: the atomics on the bitmap and the round-robin order, for A/B runs
+    t.first_flags = !getenv("SH_FIRST_FLAGS") ? -1 : on("SH_FIRST_FLAGS") ? 1 : 0;
+    t.xcd_windows = !getenv("SH_XCD_WINDOWS") || on("SH_XCD_WINDOWS");
+    if (getenv("SH_FLAG_EPOCH0")) t.flag_epoch0 = std::min(255, std::max(1, atoi(getenv("SH_FLAG_EPOCH0"))));
     return t;
 }
 

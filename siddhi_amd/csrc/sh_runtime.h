@@ -240,10 +240,18 @@ struct SlidingImpl;
 // when it is created, so a process can run queries with different settings side by side:
 // SH_DIRECT_POS=1, SH_PART_KEYS=1024, SH_NO_ASYNC_SMALL=1, SH_SL_RECORDS_SEQ=0/1, SH_AGG_BAND_ROWS=n,
 // SH_SIDE_STREAM=0 (a large push's bookkeeping back on the one stream, compaction in place),
-// SH_FOLD_GRID=0 (the multisplit fold with one workgroup per unit instead of a persistent grid)
+// SH_FOLD_GRID=0 (the multisplit fold with one workgroup per unit instead of a persistent grid),
+// SH_FIRST_FLAGS=0 / 1 (the fold marks first events always with atomics on the zeroed bitmap / always with
+// epoch bytes; unset: bytes where a push can have a mark per 32 closed events, run_closed),
+// SH_XCD_WINDOWS=0 (the persistent fold's units dealt round-robin over the XCDs instead of one contiguous
+// run each), SH_FLAG_EPOCH0=n (the first epoch byte, 1..255: a test reaches the
+// wrap in a few pushes)
 struct Tuning {
     bool side_stream = true;
     bool fold_grid = true;
+    int first_flags = -1;  // -1: chosen per push
+    bool xcd_windows = true;
+    int flag_epoch0 = 1;
     bool direct_pos = false, part_keys_1024 = false, no_async_small = false, sl_records_seq = false;
     bool pl_sort = true;   // partitioned lengthBatch keyed by the partition on the sorted lanes (lane 3)
     bool slx_wave = true;     // expired / all-events sliding replay with a wave per key (k_slx_wkey); SH_SLX_WAVE=0: a lane per key
@@ -343,6 +351,15 @@ struct sh_query {
     DevBuf blk_pass, blk_tl, blk_first, blk_xm, info, bounds, segs, seg_rows, rows, counters, out_ts, out_keys, out_vals,
         out_nulls, out_expired, out_rep, blk_cnt;
     DevBuf first_bits, word_pre;  // first-occurrence bitmap of the closed events and its word prefix
+    // First-occurrence marks as one byte per closed event (SH_FIRST_FLAGS): a set mark is the epoch of the
+    // run_closed that wrote it, so nothing is cleared from push to push. flag_epoch is the last epoch
+    // handed out (0: none yet); every run_closed that uses the flags takes the next one before anything
+    // can fail, 255 is followed by 1, and the whole capacity is zeroed when the epoch wraps and when the
+    // buffer is new (flags_zeroed / flags_zeroed_cap name the allocation last zeroed).
+    DevBuf first_flags;
+    int flag_epoch = 0;
+    const void* flags_zeroed = nullptr;
+    size_t flags_zeroed_cap = 0;
     DevBuf emit_stage;            // output rows staged at their output position (k_emit_rank)
     const void* zeroed_nulls = nullptr;    // out_nulls / out_expired buffers already zeroed
     const void* zeroed_expired = nullptr;

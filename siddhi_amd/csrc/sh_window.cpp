@@ -583,6 +583,25 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
     int64_t row_cap = 0;
     for (auto& sg : segs) row_cap += std::min<int64_t>(sg.hi - sg.lo, (int64_t)q->kt.size_ + 1);
     row_cap = std::max<int64_t>(row_cap, 1);
+    // First-occurrence marks as epoch bytes or as atomics on the zeroed bitmap. The bytes spare the fold
+    // its atomics — about 5 ns of fold per mark at C2's 3.35 M marks — and cost k_flags_tile its 32 bytes
+    // per bitmap word where k_bits_tile reads 4, about 0.15 ns per closed event (5 us per 2^25, DESIGN.md
+    // §4): they pay from one mark per 32 events. row_cap bounds the marks from above — except in a
+    // partitioned query, whose fold sees the first partition key's events only (R12) and marks few rows
+    // whatever the key table's size says; SH_FIRST_FLAGS=1 / 0 take one form always. The call's epoch is
+    // taken here, before anything can fail: a byte that a failed call may have stored is stale for the next one.
+    const bool use_flags = q->tune.first_flags > 0 ||
+                           (q->tune.first_flags < 0 && !q->partitioned && row_cap * 32 >= closed_hi);
+    if (use_flags) {
+        if (q->flag_epoch == 0) q->flag_epoch = q->tune.flag_epoch0 - 1;
+        if (q->flag_epoch >= 255) {
+            // the epochs come round again: the bytes are zeroed below, by this call or, if it fails before
+            // that, by the next one that uses them
+            q->flag_epoch = 0;
+            q->flags_zeroed = nullptr;
+        }
+        q->flag_epoch++;
+    }
     const int na = q->ap.n, nk = q->kp.n, RW = row_words(na);
     const int64_t n_words = (closed_hi >> 5) + 1;  // first-occurrence bitmap over the combined index space
     // One flat workgroup per segment walks every event of the segment, passing or not, and
@@ -594,6 +613,8 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
     const int unit_stride = agg_unit_rows(q->P, q->NL, own);
     RCHK(q->rows.reserve((size_t)n_units * unit_stride * RW * 8, false));
     RCHK(q->first_bits.reserve((size_t)n_words * 4, false));
+    // (32 bytes per bitmap word: closed_hi + 1 rounded up, so the packing kernel's 16-byte loads stay inside)
+    if (use_flags) RCHK(q->first_flags.reserve((size_t)n_words * 32, false));
     RCHK(q->counters.reserve(64 + (size_t)n_units * 4, false));
     uint32_t* unit_rows = (uint32_t*)(q->counters.as<char>() + 64);  // written by every unit's workgroup
     // a packed split (kPackIdxBits of event index per record) serves segments up to 2^22 events
@@ -607,11 +628,23 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
     if (!side) q->side_push = false;  // (the split re-run keeps the one stream, compaction included)
     hipStream_t s2 = side ? q->ctx->side_stream : s;
     if (side) HIPCHK(hipStreamWaitEvent(s2, q->ev_ms_off, 0));
-    HIPCHK(hipMemsetAsync(q->first_bits.p, 0, (size_t)n_words * 4, s2));
+    if (!use_flags) {
+        HIPCHK(hipMemsetAsync(q->first_bits.p, 0, (size_t)n_words * 4, s2));
+    } else if (q->first_flags.p != q->flags_zeroed || q->first_flags.cap != q->flags_zeroed_cap) {
+        // a wrapped epoch or a new allocation (a regrown one carries nothing over): the whole capacity, so
+        // that a later, longer push finds no byte of an epoch that comes round again
+        HIPCHK(hipMemsetAsync(q->first_flags.p, 0, q->first_flags.cap, s2));
+        q->flags_zeroed = q->first_flags.p;
+        q->flags_zeroed_cap = q->first_flags.cap;
+    }
+    const shd::FirstMarks marks{q->first_bits.as<u32>(), use_flags ? q->first_flags.as<unsigned char>() : nullptr,
+                                (u32)q->flag_epoch};
     RCHK(upload_segments(q, segs, s2));
     const Segment* dsegs = q->segs.as<Segment>();
-    SH_TRACE("run_closed nseg=%d closed_hi=%lld row_cap=%lld own=%d P=%d NL=%d ms_ready=%d", nseg, (long long)closed_hi,
-             (long long)row_cap, (int)own, q->P, q->NL, (int)q->ms_ready);
+    // (marks: the form this call took — epoch bytes or atomics — and the epoch last handed out)
+    SH_TRACE("run_closed nseg=%d closed_hi=%lld row_cap=%lld own=%d P=%d NL=%d ms_ready=%d marks=%s epoch=%d", nseg,
+             (long long)closed_hi, (long long)row_cap, (int)own, q->P, q->NL, (int)q->ms_ready,
+             use_flags ? "bytes" : "atomics", q->flag_epoch);
     if (own) {
         if (!q->ms_ready) RCHK(run_multisplit(q, closed_hi, b, false, long_seg));
         RCHK(q->seg_off.reserve((size_t)(nseg + 1) * q->P * 8, false));
@@ -632,12 +665,12 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
     HIPCHK(hipEventRecord(q->ev_agg0, s));
     launch_aggregate(s, dsegs, nseg, q->P, q->logP, q->NL, q->n_pend, q->pend_pos.as<u32>(), q->pend_vals.as<u64>(),
                      q->pend_cap, b ? q->new_pos.as<u32>() : nullptr, cs, q->ap, q->rows.as<u64>(), RW,
-                     unit_rows, q->first_bits.as<u32>(),
+                     unit_rows, marks,
                      rec_pos, own ? rec_idx : nullptr, rec_vals, (int64_t)q->rec_cap, q->seg_off.as<int64_t>(),
                      q->rec_packed,
                      EvSrc{q->n_pend, q->pend_ts.as<int64_t>(), ts, q->pend_gidx.as<u64>(),
                            q->given && b ? q->given_gidx : nullptr, q->seq},
-                     gather, q->tune.fold_grid);
+                     gather, q->tune.fold_grid, q->tune.xcd_windows);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(q->ev_agg1, s));
     // output columns sized for the row capacity; the emit kernels read the row count on the device
@@ -669,8 +702,7 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
             q->head_queued = true;
         }
     }
-    launch_bits_prefix(s, q->first_bits.as<u32>(), n_words, q->blk_cnt.as<int64_t>(), q->word_pre.as<u64>(),
-                       q->counters.as<u32>(), to);
+    launch_bits_prefix(s, marks, n_words, q->blk_cnt.as<int64_t>(), q->word_pre.as<u64>(), q->counters.as<u32>(), to);
     if (gather)
         launch_emit_gather(s, q->word_pre.as<u64>(), n_words, dsegs, nseg, q->P, q->logP, unit_stride, q->rows.as<u64>(),
                            RW, pos_src(q, b), q->pend_pos.as<u32>(), q->n_pend, q->counters.as<u32>(), na, q->kt.dev(),
