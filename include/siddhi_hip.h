@@ -85,6 +85,9 @@ typedef struct {
                                    the timeout through sh_query_set_ext_timeout */
 #define SH_WIN_EXT_TIME 5     /* core/query/processor/stream/window/ExternalTimeWindowProcessor.java:
                                  externalTime(ts_col, T) — sliding over the LONG attribute ts_col    */
+#define SH_WIN_LENGTH 6       /* core/query/processor/stream/window/LengthWindowProcessor.java:106-142:
+                                 length(N) — sliding over the last N passing events; window_param = N
+                                 (1 .. 2^31 - 1); an older library answers SH_ERR_UNSUPPORTED           */
 
 /* ---- aggregators: core/query/selector/attribute/aggregator/ [Sum,Avg,Count,Min,Max]AttributeAggregatorExecutor ---- */
 #define SH_AGG_SUM 1

@@ -29,6 +29,7 @@ OP_KEY, OP_AGG = 12, 13  # operands of a having program (sh_query_set_having)
 CMP_OPS = {">": OP_GT, ">=": OP_GE, "<": OP_LT, "<=": OP_LE, "==": OP_EQ, "!=": OP_NE}
 
 WIN_NONE, WIN_LENGTH_BATCH, WIN_TIME_BATCH, WIN_TIME, WIN_EXT_TIME_BATCH, WIN_EXT_TIME = 0, 1, 2, 3, 4, 5
+WIN_LENGTH = 6  # sliding length(N): LengthWindowProcessor
 AGG_SUM, AGG_AVG, AGG_COUNT, AGG_MIN, AGG_MAX = 1, 2, 3, 4, 5
 AGG_NAMES = {"sum": AGG_SUM, "avg": AGG_AVG, "count": AGG_COUNT, "min": AGG_MIN, "max": AGG_MAX}
 DUR_SECONDS, DUR_MINUTES, DUR_HOURS, DUR_DAYS, DUR_MONTHS, DUR_YEARS = range(6)
@@ -209,7 +210,7 @@ def compile_having(spec, expr) -> List[FilterOp]:
 class QuerySpec:
     """`from S[filter]#window.kind(param...) select group..., aggs... group by group... insert ...`"""
     schema: Schema
-    window: Optional[str]            # 'lengthBatch' | 'timeBatch' | 'time' | None (no window)
+    window: Optional[str]            # 'lengthBatch' | 'timeBatch' | 'time' | 'length' | ... | None (no window)
     param: int = 0
     group_by: Sequence[str] = ()
     aggs: Sequence[tuple] = ()       # (fn_name, column or None)
@@ -242,7 +243,7 @@ class QuerySpec:
         d.filter = C.cast(arr, C.POINTER(FilterOp))
         d.window = {None: WIN_NONE, "lengthBatch": WIN_LENGTH_BATCH, "timeBatch": WIN_TIME_BATCH,
                     "time": WIN_TIME, "externalTimeBatch": WIN_EXT_TIME_BATCH,
-                    "externalTime": WIN_EXT_TIME}[self.window]
+                    "externalTime": WIN_EXT_TIME, "length": WIN_LENGTH}[self.window]
         d.window_param = self.param
         d.stream_current = int(self.stream_current)
         d.has_start_time = int(self.start_time is not None)

@@ -28,6 +28,7 @@ const char* window_name(int w) {
         case SH_WIN_NONE: return "no window";
         case SH_WIN_TIME: return "a sliding time window";
         case SH_WIN_EXT_TIME: return "a sliding externalTime window";
+        case SH_WIN_LENGTH: return "a sliding length window";
         default: return "this window";
     }
 }

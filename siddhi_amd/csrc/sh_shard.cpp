@@ -108,6 +108,9 @@ static int shard_create(sh_ctx* ctx, const sh_query_desc* d, const KeyPlan* kp_o
     if (!ctx || !d || !out) return sh_fail(SH_ERR_INVALID, "sh_shard_create: NULL argument");
     if (world < 1 || world > kMaxShards || rank < 0 || rank >= world)
         return sh_fail(SH_ERR_INVALID, "sh_shard_create: need 0 <= rank < world <= 16");
+    // (the ordinal of an event counts every key's passing events: the owners would need the global rank)
+    if (d->window == SH_WIN_LENGTH)
+        return sh_fail(SH_ERR_UNSUPPORTED, "a sliding length window is not sharded: its clock is the global count of passing events");
     if (d->window != SH_WIN_TIME_BATCH && d->window != SH_WIN_LENGTH_BATCH && d->window != SH_WIN_TIME)
         return sh_fail(SH_ERR_UNSUPPORTED, "sharded ingest runs timeBatch / lengthBatch / time group-by queries");
     if (d->window == SH_WIN_TIME && (d->partition_col >= 0 || kp_override))

@@ -1,5 +1,7 @@
 // sh_sliding.cpp — sliding `from S[cond]#window.time(T) select k, aggs group by k insert into O`
-// (TimeWindowProcessor + QuerySelector in SLIDE mode) behind sh_query_* (kind 1).
+// (TimeWindowProcessor + QuerySelector in SLIDE mode) behind sh_query_* (kind 1); externalTime(ts, T)
+// and length(N) run the same rings with another clock (the attribute's running maximum; the count of
+// passing events, LengthWindowProcessor.java:106-142).
 //
 // The window contents of every key live on the device in per-key rings; aggregator state per key
 // (counts, running sums with Java's residue, min/max deques) persists across pushes. A push emits,
@@ -207,8 +209,10 @@ static int sliding_rekey(sh_query* q) {
         launch_slx_rekey_map(st, size, q->kt.dev(), nk.dev(), s->rlen.as<int64_t>(), s->cnt.as<int64_t>(),
                              s->f.as<u64>(), n, q->ap, map.as<u32>());
     else
+        // (length(N): the ring holds ordinals and the next event's clock is the passing count so far)
         launch_sl_rekey_map(st, size, q->kt.dev(), nk.dev(), s->rhead.as<int64_t>(), s->rlen.as<int64_t>(),
-                            s->rpm.as<int64_t>(), s->rc, q->d.window_param, q->clock, map.as<u32>());
+                            s->rpm.as<int64_t>(), s->rc, q->d.window_param,
+                            q->d.window == SH_WIN_LENGTH ? s->npass : q->clock, map.as<u32>());
     HIPCHK(hipGetLastError());
     RCHK(nk.check(st));
     const int64_t F = std::max(1, q->ap.n_fields), V = std::max(1, q->ap.n_vcols), rc = s->rc;
@@ -249,7 +253,8 @@ int sliding_push(sh_query* q, const sh_batch* b, bool host_out, const sh_out** o
     // hysteresis: after a rebuild that kept many live keys, the next one waits until size/8 more keys
     // arrived (capped at 7/8 full), instead of copying every slot's state on every push
     const int64_t tsz = (int64_t)q->kt.size_;
-    if (!q->kt.dense && q->kp.n > 0 && (q->d.window == SH_WIN_TIME || s->xm) && q->clock_valid &&
+    if (!q->kt.dense && q->kp.n > 0 && (q->d.window == SH_WIN_TIME || q->d.window == SH_WIN_LENGTH || s->xm) &&
+        q->clock_valid &&
         q->kt.n_keys > std::max<int64_t>(tsz / 2, s->rekey_floor)) {
         RCHK(sliding_rekey(q));
         s->rekey_floor = std::min<int64_t>(q->kt.n_keys + tsz / 8, tsz * 7 / 8);
@@ -264,7 +269,7 @@ int sliding_push(sh_query* q, const sh_batch* b, bool host_out, const sh_out** o
     RCHK(s->blk_tl.reserve(nblk * 8, false));
     RCHK(s->blk_pm.reserve(nblk * 8, false));
     WinParams wp{};
-    wp.kind = q->d.window;  // SH_WIN_TIME or SH_WIN_EXT_TIME
+    wp.kind = q->d.window;  // SH_WIN_TIME, SH_WIN_EXT_TIME or SH_WIN_LENGTH
     wp.ts_col = q->d.ts_col;
     wp.clock_valid = q->clock_valid;
     wp.clock0 = q->clock;
@@ -292,10 +297,12 @@ int sliding_push(sh_query* q, const sh_batch* b, bool host_out, const sh_out** o
         RCHK(s->rec_aos.reserve((size_t)N * kSlAosWords * 8, false));
         rec.aos = s->rec_aos.as<u64>();
     }
-    const bool ext = q->d.window == SH_WIN_EXT_TIME;
+    // externalTime / length: the records' clock is not the playback clock, which rows take from rec_sclk
+    const bool len = q->d.window == SH_WIN_LENGTH;
+    const bool ext = q->d.window == SH_WIN_EXT_TIME || len;
     if (ext) RCHK(s->rec_sclk.reserve(N * 8, false));
     launch_sl_records(st, b->ts, cs, q->fp, wp, q->kp, q->kt.dev(), q->ap, s->blk_pass.as<int64_t>(),
-                      s->blk_tl.as<int64_t>(), s->blk_pm.as<int64_t>(), s->pm, rec,
+                      s->blk_tl.as<int64_t>(), s->blk_pm.as<int64_t>(), len ? s->npass : s->pm, rec,
                       pre ? nullptr : s->slot_cnt.as<u32>(), nblk, ext ? s->rec_sclk.as<int64_t>() : nullptr);
     HIPCHK(hipMemsetAsync((char*)s->info.p + offsetof(SlInfo, need), 0, 8, st));
     int64_t* need_dev = (int64_t*)((char*)s->info.p + offsetof(SlInfo, need));
@@ -319,6 +326,7 @@ int sliding_push(sh_query* q, const sh_batch* b, bool host_out, const sh_out** o
     q->clock = q->clock_valid ? std::max(q->clock, info.max_tl) : info.max_tl;
     q->clock_valid = true;
     s->pm = std::max(s->pm, info.max_pm);
+    s->npass += info.total_pass;
     s->send_base += b->send_size > 0 ? (N + b->send_size - 1) / b->send_size : 1;
     q->stats.events = N;
     return SH_OK;
@@ -489,7 +497,8 @@ static int sliding_finish(sh_query* q, int64_t M, int64_t rec_cap, int64_t need,
                        q->kp, cap, s->out_ts.as<int64_t>(), s->out_keys.as<int64_t>(), s->out_vals.as<u64>(),
                        s->out_nulls.as<unsigned char>(), s->out_send.as<int64_t>(), s->out_clock.as<int64_t>(),
                        s->rec_raw.as<u32>(), raw_base, want_order ? q->out_order.as<int64_t>() : nullptr,
-                       q->d.window == SH_WIN_EXT_TIME ? s->rec_sclk.as<int64_t>() : nullptr, s->out_rep.as<int64_t>());
+                       q->d.window == SH_WIN_EXT_TIME || q->d.window == SH_WIN_LENGTH ? s->rec_sclk.as<int64_t>() : nullptr,
+                       s->out_rep.as<int64_t>());
         HIPCHK(hipGetLastError());
     }
     // flush structure: a flush per send that produced rows (one selector output chunk per send)
@@ -665,7 +674,9 @@ static int slx_run(sh_query* q, const sh_batch* b, int64_t now, bool host_out, c
     SlidingImpl* s = q->sl;
     hipStream_t st = q->ctx->stream;
     q->stats = sh_stats{};
-    const bool ext = q->d.window == SH_WIN_EXT_TIME;
+    // length(N): no scheduler either, and every expiry point is arithmetic (sh_length_kernels.hip)
+    const bool len = q->d.window == SH_WIN_LENGTH;
+    const bool ext = q->d.window == SH_WIN_EXT_TIME || len;
     const int64_t T = q->d.window_param;
     const int64_t N = b ? b->n : 0;
     const int64_t ss = b ? b->send_size : 0;
@@ -717,7 +728,7 @@ static int slx_run(sh_query* q, const sh_batch* b, int64_t now, bool host_out, c
         // from the sorted slots instead of per-slot counts)
         presorted = q->ap.n > 0 && sl_records_seq_applies(q->fp, wp, q->ap);
         launch_sl_records(st, b->ts, cs, q->fp, wp, q->kp, q->kt.dev(), q->ap, s->blk_pass.as<int64_t>(),
-                          s->blk_tl.as<int64_t>(), s->blk_pm.as<int64_t>(), s->pm, rec,
+                          s->blk_tl.as<int64_t>(), s->blk_pm.as<int64_t>(), len ? s->npass : s->pm, rec,
                           presorted ? nullptr : s->slot_cnt.as<u32>(), nblk, ext ? s->rec_sclk.as<int64_t>() : nullptr);
         HIPCHK(hipMemsetAsync((char*)s->info.p + offsetof(SlInfo, need), 0, 8, st));
         int64_t* need_dev = (int64_t*)((char*)s->info.p + offsetof(SlInfo, need));
@@ -812,7 +823,7 @@ static int slx_run(sh_query* q, const sh_batch* b, int64_t now, bool host_out, c
     s->useq.used = (size_t)W0 * 8;
     RCHK(s->upm.reserve(std::max<int64_t>(n_u, 1) * 8, true));
     RCHK(s->useq.reserve(std::max<int64_t>(n_u, 1) * 8, true));
-    launch_slx_append(st, rec.pm, rec.raw, M, q->seq, s->upm.as<int64_t>() + W0, s->useq.as<int64_t>() + W0);
+    if (!len) launch_slx_append(st, rec.pm, rec.raw, M, q->seq, s->upm.as<int64_t>() + W0, s->useq.as<int64_t>() + W0);
     const int64_t nu1 = std::max<int64_t>(n_u, 1);
     const int na = q->ap.n;
     // the wave-per-key replay reads one record per add (xa) and per window position (xx) and writes one
@@ -832,12 +843,19 @@ static int slx_run(sh_query* q, const sh_batch* b, int64_t now, bool host_out, c
     RCHK(s->x_bnd.reserve((size_t)(3 * (nu1 / kBlock + 2) + cap / kBlock + 2) * 8, false));
     HIPCHK(hipMemsetAsync(s->x_nexp.p, 0, 8, st));
     const int64_t* rsclk = ext ? s->rec_sclk.as<int64_t>() : nullptr;
-    launch_slx_expiry(st, s->upm.as<int64_t>(), n_u, W0, M, rec.clock, rsclk, rec.raw, ss, s->x_fK.as<int64_t>(),
-                      s->x_fC.as<int64_t>(), s->x_fS.as<int64_t>(), nF, T, s->x_xop.as<u64>(), s->x_xch.as<int64_t>(),
-                      s->x_xts.as<int64_t>(), s->x_xclk.as<int64_t>(), (unsigned long long*)s->x_nexp.p,
-                      wave ? s->x_xx.as<u64>() : nullptr, s->useq.as<int64_t>(), rec.vals, s->x_bnd.as<int64_t>());
-    launch_slx_aop(st, rec.clock, M, s->upm.as<int64_t>(), n_u, W0, T, s->x_aop.as<u64>(),
-                   wave ? s->x_xa.as<u64>() : nullptr, rec, rsclk, s->x_bnd.as<int64_t>() + 3 * (nu1 / kBlock + 2));
+    if (len) {
+        launch_len_ops(st, n_u, W0, M, s->x0, s->g0, T, q->seq, ss, rec, rsclk, s->upm.as<int64_t>(),
+                       s->useq.as<int64_t>(), s->x_xop.as<u64>(), s->x_xch.as<int64_t>(), s->x_xts.as<int64_t>(),
+                       s->x_xclk.as<int64_t>(), s->x_aop.as<u64>(), wave ? s->x_xx.as<u64>() : nullptr,
+                       wave ? s->x_xa.as<u64>() : nullptr);
+    } else {
+        launch_slx_expiry(st, s->upm.as<int64_t>(), n_u, W0, M, rec.clock, rsclk, rec.raw, ss, s->x_fK.as<int64_t>(),
+                          s->x_fC.as<int64_t>(), s->x_fS.as<int64_t>(), nF, T, s->x_xop.as<u64>(), s->x_xch.as<int64_t>(),
+                          s->x_xts.as<int64_t>(), s->x_xclk.as<int64_t>(), (unsigned long long*)s->x_nexp.p,
+                          wave ? s->x_xx.as<u64>() : nullptr, s->useq.as<int64_t>(), rec.vals, s->x_bnd.as<int64_t>());
+        launch_slx_aop(st, rec.clock, M, s->upm.as<int64_t>(), n_u, W0, T, s->x_aop.as<u64>(),
+                       wave ? s->x_xa.as<u64>() : nullptr, rec, rsclk, s->x_bnd.as<int64_t>() + 3 * (nu1 / kBlock + 2));
+    }
     // the push's records sorted stably by key slot: each key's adds in arrival order
     if (!presorted) {
         RCHK(s->ranks.reserve(cap * 4, false));
@@ -848,8 +866,10 @@ static int slx_run(sh_query* q, const sh_batch* b, int64_t now, bool host_out, c
     RCHK(s->tmp.reserve((size_t)((s->nslots + 1 + kTile - 1) / kTile + 16) * 8, false));
     launch_slx_keyoff(st, s->slot_cnt.as<u32>(), s->nslots, s->key_off.as<u32>(), s->tmp.as<int64_t>());
     HIPCHK(hipGetLastError());
+    // (length(N): arrivals below g0 + M - N have left — no count to read back)
     int64_t R = 0;
-    RCHK(read_count(q, (const int64_t*)s->x_nexp.p, &R));
+    if (len) R = std::min(n_u, std::max<int64_t>(0, s->g0 + M - T - s->x0));
+    else RCHK(read_count(q, (const int64_t*)s->x_nexp.p, &R));
     // ---- the replay (one lane per key slot) writes one row per (chunk, key) at its operation index
     const int64_t n_ops = M + R;
     const int64_t oc = std::max<int64_t>(n_ops, 1);
@@ -878,8 +898,7 @@ static int slx_run(sh_query* q, const sh_batch* b, int64_t now, bool host_out, c
     if (q->ap.n == 0)
         launch_slx_pass(st, rec, M, s->x_aop.as<u64>(), s->x_xop.as<u64>(), s->x_xch.as<int64_t>(),
                         s->x_xts.as<int64_t>(), s->x_xclk.as<int64_t>(), s->useq.as<int64_t>(), n_u, q->seq, ss,
-                        q->d.current_on, q->d.expired_on, rows, s->flags.as<unsigned char>(),
-                        ext ? s->rec_sclk.as<int64_t>() : nullptr);
+                        q->d.current_on, q->d.expired_on, rows, s->flags.as<unsigned char>(), rsclk);
     else if (wave)
         launch_slx_wkey(st, s->key_off.as<u32>(), s->ranks.as<u32>(), s->nslots, s->x_xa.as<u64>(), s->x_xx.as<u64>(),
                         n_u, s->x0, s->g0, q->seq, ss, state_of(s), s->rg.as<int64_t>(), q->ap, q->d.current_on,
@@ -938,6 +957,7 @@ static int slx_run(sh_query* q, const sh_batch* b, int64_t now, bool host_out, c
     }
     s->x0 += R;
     s->g0 += M;
+    s->npass += M;
     s->w0 = new_w;
     if (b) {
         q->seq += N;
@@ -971,7 +991,8 @@ int sliding_advance(sh_query* q, int64_t now, const sh_out** out, bool host_out)
 
 // Persistent buffers of the sliding state and their byte sizes, for sh_query_snapshot/restore
 // (sh_snapshot.cpp). scalars = {nslots, rc, pm, send_base}; with set = true the ring capacity is
-// first made `new_rc` and the scalars are taken from the snapshot.
+// first made `new_rc` and the scalars are taken from the snapshot. (A length window's lifetime count of
+// passing events travels beside them: sliding_length_count.)
 int sliding_state_buffers(sh_query* q, std::vector<std::pair<DevBuf*, size_t>>& bufs, int64_t* sc, int n_sc, bool set,
                           int64_t new_rc) {
     SlidingImpl* s = q->sl;
@@ -993,6 +1014,8 @@ int sliding_state_buffers(sh_query* q, std::vector<std::pair<DevBuf*, size_t>>& 
             {&s->cur_send, n * 8},     {&s->cur_first, n * 8}};
     return SH_OK;
 }
+
+int64_t* sliding_length_count(sh_query* q) { return &q->sl->npass; }
 
 // Checkpoint of the expiry FIFO of `insert expired / all events` and pass-through sliding windows
 // (sh_slx_kernels.hip): arrival indices X0 / G0, the unexpired FIFO (PM, stream index), the pending

@@ -179,6 +179,11 @@ void launch_slx_emit_aos(hipStream_t s, const unsigned char* flags, i64 n, const
 void launch_slx_emit(hipStream_t s, const unsigned char* flags, i64 n, const i64* blk_pre, int nblk, SlxRows rows,
                      int n_aggs, KeyTable kt, KeyPlan kp, i64 out_cap, i64* out_ts, i64* out_keys, u64* out_vals,
                      unsigned char* out_nulls, unsigned char* out_exp, i64* out_ch, i64* out_clock, i64* out_rep);
+// length(N): the same outputs as launch_slx_append + launch_slx_expiry + launch_slx_aop, in closed form
+// (sh_length_kernels.hip); xx / xa non-null: the record forms, else the columns
+void launch_len_ops(hipStream_t s, i64 n_u, i64 W0, i64 M, i64 X0, i64 G0, i64 L, i64 seq_base, i64 send_size,
+                    SlRecords rec, const i64* rsclk, i64* upm, i64* useq, u64* xop, i64* xch, i64* xts, i64* xclk,
+                    u64* aop, u64* xx, u64* xa);
 void launch_slx_shift(hipStream_t s, const i64* upm, const i64* useq, i64 from, i64 n, i64* opm, i64* oseq);
 void launch_slx_rekey_map(hipStream_t s, i64 size, KeyTable old_kt, KeyTable new_kt, const i64* rlen, const i64* cnt,
                           const u64* f, i64 nslots, AggPlan ap, u32* map);

@@ -1,4 +1,4 @@
-// sh_sliding_impl.h — host state of a query of kind 1 (sh_sliding.cpp: time / externalTime windows;
+// sh_sliding_impl.h — host state of a query of kind 1 (sh_sliding.cpp: time / externalTime / length windows;
 // sh_plane.cpp: partitioned lengthBatch / time windows keyed by the partition).
 #pragma once
 #include <cstdint>
@@ -31,6 +31,7 @@ struct SlidingImpl {
     int P = 1, logP = 0;
     int64_t pm = INT64_MIN;   // PM carried across pushes
     int64_t send_base = 0;    // global send number of the push's first send
+    int64_t npass = 0;        // passing events of the query's lifetime: length(N)'s clock, the next push's ordinal base
     int64_t rekey_floor = 0;  // key count above which the next key-table rebuild runs (hysteresis)
     DevBuf cnt, f, mm, mm_has, dq_head, dq_len, dq, rhead, rlen, rpm, rval, cur_send, cur_first;
     // per push scratch

@@ -26,13 +26,14 @@ __global__ __launch_bounds__(kBlock) void k_sl_blockagg(const i64* __restrict__ 
     bool pass[kItems];
     filter_items(f, cols, base, wp.N, pass);
     // externalTime: PM runs over the timestamp attribute instead of the event timestamps
-    const bool ext = wp.kind == SH_WIN_EXT_TIME;
+    // (length(N): PM is the ordinal of the passing event, base + rank — no maximum to carry)
+    const bool ext = wp.kind == SH_WIN_EXT_TIME, len = wp.kind == SH_WIN_LENGTH;
 #pragma unroll
     for (int i = 0; i < kItems; i++) {
         i64 e = base + i;
         if (e < wp.N) {
             i64 t = ts[e];
-            if (pass[i]) { cnt++; pm = max(pm, ext ? load_raw(cols, wp.ts_col, e) : t); }
+            if (pass[i]) { cnt++; if (!len) pm = max(pm, ext ? load_raw(cols, wp.ts_col, e) : t); }
             if (is_send_last(wp, e)) tl = max(tl, t);
         }
     }
@@ -101,20 +102,23 @@ __global__ __launch_bounds__(kBlock) void k_sl_records(const i64* __restrict__ t
     bool pass[kItems];
     i64 cnt = 0, tl = INT64_MIN, pm = INT64_MIN;
     filter_items(f, cols, base, wp.N, pass);
-    const bool ext = wp.kind == SH_WIN_EXT_TIME;
+    const bool ext = wp.kind == SH_WIN_EXT_TIME, len = wp.kind == SH_WIN_LENGTH;
 #pragma unroll
     for (int i = 0; i < kItems; i++) {
         i64 e = base + i;
         if (e < wp.N) {
             i64 t = ts[e];
             cnt += pass[i];
-            if (pass[i]) pm = max(pm, ext ? load_raw(cols, wp.ts_col, e) : t);
+            if (pass[i] && !len) pm = max(pm, ext ? load_raw(cols, wp.ts_col, e) : t);
             if (is_send_last(wp, e)) tl = max(tl, t);
         }
     }
     i64 r = block_excl_scan(cnt, SumOp(), 0, nullptr) + blk_pass_pre[blockIdx.x];
     i64 cm = max(block_excl_scan(tl, MaxOp(), INT64_MIN, nullptr), blk_tl_pre[blockIdx.x]);
-    i64 pmx = max(max(block_excl_scan(pm, MaxOp(), INT64_MIN, nullptr), blk_pm_pre[blockIdx.x]), pm0);
+    // length(N) (LengthWindowProcessor :106-142): the clock is the count of passing events, so the PM and
+    // the clock of a record are its ordinal pm0 + rank (pm0 = the passing events of earlier pushes) and
+    // "PM(j) + N <= clock(i)" is j <= i - N; no max-scan of the timestamps
+    i64 pmx = len ? 0 : max(max(block_excl_scan(pm, MaxOp(), INT64_MIN, nullptr), blk_pm_pre[blockIdx.x]), pm0);
     const i64 c0 = wp.clock_valid ? wp.clock0 : INT64_MIN;
 #pragma unroll
     for (int i = 0; i < kItems; i++) {
@@ -127,9 +131,9 @@ __global__ __launch_bounds__(kBlock) void k_sl_records(const i64* __restrict__ t
             // externalTime (ExternalTimeWindowProcessor :126-161): an event expires the queue head
             // while headTime + T <= its own attribute, so event j has left the window at event i iff
             // PMa(j) + T <= PMa(i) (PMa = running max of the attribute): clock = PMa(i)
-            pmx = max(pmx, ext ? load_raw(cols, wp.ts_col, e) : t);
+            pmx = len ? pm0 + r : max(pmx, ext ? load_raw(cols, wp.ts_col, e) : t);
             const i64 sclk = max(c0, max(cm, ts[send_last_of(wp, e)]));
-            i64 clk = ext ? pmx : sclk;
+            i64 clk = ext || len ? pmx : sclk;
             if (send_clock) send_clock[r] = sclk;  // the flush clock of an externalTime row
             pos = key_slot(kt, make_key(kp, cols, e));
             rec.raw[r] = (u32)e;
@@ -181,6 +185,10 @@ __global__ __launch_bounds__(kBlock) void k_sl_records_seq(const i64* __restrict
     i64 carry_cm = blk_tl_pre[blockIdx.x];
     i64 carry_pm = max(blk_pm_pre[blockIdx.x], pm0);
     const i64 c0 = wp.clock_valid ? wp.clock0 : INT64_MIN;
+    // length(N): every event passes, so a record's clock and PM are its ordinal pm0 + r and the block
+    // max-scan below only serves the send's playback clock (column records only: the keyed replay's
+    // 48-byte records hold one clock, and a length row's flush clock is not its expiry clock)
+    const bool len = wp.kind == SH_WIN_LENGTH;
     const int lane = threadIdx.x & 63, wb = threadIdx.x & ~63;
     for (int it = 0; it < kItems; it++) {
         const i64 e = tile0 + (i64)it * kBlock + threadIdx.x;
@@ -213,14 +221,14 @@ __global__ __launch_bounds__(kBlock) void k_sl_records_seq(const i64* __restrict
             for (int q = lane; q < nw * 3; q += 64) dst[q] = stg[wb * 3 + q];
             __syncthreads();
         } else if (in) {
-            const i64 pmx = max(carry_pm, incl);
-            const i64 sclk = max(c0, max(carry_cm, incl));
             const i64 r = r0 + (i64)it * kBlock + threadIdx.x;
+            const i64 pmx = len ? pm0 + r : max(carry_pm, incl);
+            const i64 sclk = max(c0, max(carry_cm, incl));
             if (send_clock) send_clock[r] = sclk;
             rec.raw[r] = (u32)e;
             rec.slot[r] = pos;
             {
-                rec.clock[r] = sclk;
+                rec.clock[r] = len ? pmx : sclk;
                 rec.pm[r] = pmx;
                 rec.ts[r] = t;
                 for (int j = 0; j < ap.n_vcols; j++) rec.vals[(size_t)j * rec.cap + r] = (u64)load_raw(cols, ap.vcol_src[j], e);
@@ -237,7 +245,8 @@ __global__ __launch_bounds__(kBlock) void k_sl_records_seq(const i64* __restrict
 }
 
 bool sl_records_seq_applies(FilterProg f, WinParams wp, AggPlan ap) {
-    return filter_kind(f) == 0 && wp.send_size == 1 && wp.kind == SH_WIN_TIME && ap.n_vcols >= 1 && wp.rec_seq;
+    return filter_kind(f) == 0 && wp.send_size == 1 && (wp.kind == SH_WIN_TIME || wp.kind == SH_WIN_LENGTH) &&
+           ap.n_vcols >= 1 && wp.rec_seq;
 }
 
 void launch_sl_records(hipStream_t s, const i64* ts, ColSet cols, FilterProg f, WinParams wp, KeyPlan kp,

@@ -439,6 +439,7 @@ struct SlidingImpl;
 int sliding_state_buffers(sh_query* q, std::vector<std::pair<DevBuf*, size_t>>& bufs, int64_t* scalars, int n_scalars,
                           bool set, int64_t new_rc);
 int sliding_fifo_state(sh_query* q, std::vector<std::pair<DevBuf*, size_t>>& bufs, int64_t* sc, bool set, int* kind);
+int64_t* sliding_length_count(sh_query* q);
 void plane_state_buffers(sh_query* q, std::vector<std::pair<DevBuf*, size_t>>& bufs);
 int plane_host_save(sh_query* q, std::vector<uint8_t>& out);
 int plane_host_load(sh_query* q, const uint8_t* p, size_t n, size_t* used);
@@ -455,6 +456,9 @@ int sliding_snapshot(sh_query* q, Writer& w) {
     std::vector<std::pair<DevBuf*, size_t>> bufs;
     RCHK(sliding_state_buffers(q, bufs, sc, 4, false, 0));
     for (int i = 0; i < 4; i++) w.val<int64_t>(sc[i]);
+    // length(N): the lifetime count of passing events — the window's clock, which the rings' ordinals and
+    // the expiry FIFO are read against (other windows' blobs keep their layout)
+    if (q->d.window == SH_WIN_LENGTH) w.val<int64_t>(*sliding_length_count(q));
     for (auto& b : bufs) RCHK(w.dev(b.first->p, b.second, s));
     // the expiry FIFO of expired / all-events output and pass-through windows
     int64_t fs[5] = {0, 0, 0, 0, 0};
@@ -489,7 +493,10 @@ int sliding_restore(sh_query* q, Reader& r) {
     q->kt.n_keys = nk;
     int64_t sc[4];
     for (int i = 0; i < 4; i++) sc[i] = r.val<int64_t>();
+    const int64_t len_count = q->d.window == SH_WIN_LENGTH ? r.val<int64_t>() : 0;
     if (!r.ok) return sh_fail(SH_ERR_INVALID, "snapshot blob truncated");
+    if (len_count < 0) return sh_fail(SH_ERR_INVALID, "snapshot does not match this query");
+    if (q->d.window == SH_WIN_LENGTH) *sliding_length_count(q) = len_count;
     std::vector<std::pair<DevBuf*, size_t>> bufs;
     RCHK(sliding_state_buffers(q, bufs, sc, 4, true, sc[1]));
     for (auto& b : bufs) RCHK(r.dev(*b.first, b.second, s));

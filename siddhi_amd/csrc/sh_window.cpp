@@ -287,15 +287,15 @@ static int query_create(sh_ctx* ctx, const sh_query_desc* d, const KeyPlan* kp_o
     const bool batch_win = d->window == SH_WIN_LENGTH_BATCH || d->window == SH_WIN_TIME_BATCH;
     const bool pass_through = d->n_aggs == 0 && d->n_group_by == 0 && d->partition_col < 0 &&
                               (batch_win || d->window == SH_WIN_EXT_TIME_BATCH || d->window == SH_WIN_TIME ||
-                               d->window == SH_WIN_EXT_TIME);
+                               d->window == SH_WIN_EXT_TIME || d->window == SH_WIN_LENGTH);
     if ((d->n_aggs < 1 && !pass_through) || d->n_aggs > SH_MAX_AGGS)
         return sh_fail(SH_ERR_UNSUPPORTED,
                        "GPU path runs aggregation queries (1..8 aggregators) or pass-through lengthBatch / timeBatch / "
-                       "time / externalTime windows");
+                       "time / externalTime / length windows");
     if (d->window != SH_WIN_LENGTH_BATCH && d->window != SH_WIN_TIME_BATCH && d->window != SH_WIN_TIME &&
-        d->window != SH_WIN_EXT_TIME_BATCH && d->window != SH_WIN_EXT_TIME)
+        d->window != SH_WIN_EXT_TIME_BATCH && d->window != SH_WIN_EXT_TIME && d->window != SH_WIN_LENGTH)
         return sh_fail(SH_ERR_UNSUPPORTED,
-                       "GPU path needs a lengthBatch, timeBatch, time, externalTimeBatch or externalTime window");
+                       "GPU path needs a lengthBatch, timeBatch, time, externalTimeBatch, externalTime or length window");
     if (d->window == SH_WIN_EXT_TIME &&
         (d->ts_col < 0 || d->ts_col >= d->n_cols || d->col_types[d->ts_col] != SH_T_LONG))
         return sh_fail(SH_ERR_INVALID, "externalTime timestamp must be a long attribute");
@@ -308,7 +308,16 @@ static int query_create(sh_ctx* ctx, const sh_query_desc* d, const KeyPlan* kp_o
     }
     if (d->window_param <= 0) return sh_fail(SH_ERR_INVALID, "window length/period must be > 0");
     if (!d->current_on && !d->expired_on) return sh_fail(SH_ERR_INVALID, "query emits neither current nor expired events");
-    const bool sliding_win = d->window == SH_WIN_TIME || d->window == SH_WIN_EXT_TIME;
+    if (d->window == SH_WIN_LENGTH) {
+        // LengthWindowProcessor's parameter is a Java int; length(0) takes its third branch (:123-137:
+        // current, its own expired copy, RESET) and stays refused with the window_param <= 0 above
+        if (d->window_param > 0x7FFFFFFFll) return sh_fail(SH_ERR_INVALID, "length(N): N is a Java int, at most 2^31 - 1");
+        if (d->partition_col >= 0)
+            return sh_fail(SH_ERR_UNSUPPORTED, "partition with around a sliding length window is not on the GPU");
+        if (d->stream_current)
+            return sh_fail(SH_ERR_UNSUPPORTED, "stream.current.event has no meaning on a sliding length window");
+    }
+    const bool sliding_win = d->window == SH_WIN_TIME || d->window == SH_WIN_EXT_TIME || d->window == SH_WIN_LENGTH;
     // partitioned lengthBatch / time keyed by the partition (no group-by, or group by the partition
     // key): one lane per partition (sh_plane.cpp)
     const bool by_partition = d->n_group_by == 0 || (d->n_group_by == 1 && d->group_by[0] == d->partition_col);
@@ -338,8 +347,8 @@ static int query_create(sh_ctx* ctx, const sh_query_desc* d, const KeyPlan* kp_o
         !((batch_win || sliding_win || d->window == SH_WIN_EXT_TIME_BATCH) && d->partition_col < 0) && !plane &&
         !r12_batch)
         return sh_fail(SH_ERR_UNSUPPORTED,
-                       "expired / all-events output runs on lengthBatch, timeBatch, externalTimeBatch, time and "
-                       "externalTime windows (partitioned: timeBatch, lengthBatch, and time grouped by the partition key)");
+                       "expired / all-events output runs on lengthBatch, timeBatch, externalTimeBatch, time, "
+                       "externalTime and length windows (partitioned: timeBatch, lengthBatch, and time grouped by the partition key)");
     // (partitioned: lengthBatch lanes, every event its own chunk of one key)
     if (d->stream_current &&
         !(batch_win && d->n_aggs >= 1 && (d->partition_col < 0 || (plane && d->window == SH_WIN_LENGTH_BATCH) || plane_tbsc)))
@@ -422,7 +431,7 @@ static int query_create(sh_ctx* ctx, const sh_query_desc* d, const KeyPlan* kp_o
     }
     q->partitioned = d->partition_col >= 0 && !plane;
     q->xmode = d->expired_on != 0 && !d->stream_current;
-    if (d->window == SH_WIN_TIME || d->window == SH_WIN_EXT_TIME || plane) {
+    if (sliding_win || plane) {
         q->kind = 1;
         if ((rc = sliding_create(q))) { delete q; return rc; }
         *out = q;
