@@ -310,6 +310,58 @@ int sh_query_set_having(sh_query* q, const sh_filter_op* ops, int32_t n_ops);
  * (the same validation code): the shim calls it at parse time to decide whether the query goes to the GPU. */
 int sh_having_check(const sh_query_desc* desc, const sh_filter_op* ops, int32_t n_ops);
 
+/* `order by` / `limit` / `offset` of the selector, on the GPU: the last step of QuerySelector.processInBatchGroupBy
+ * (core/query/selector/QuerySelector.java:355-370; processNoGroupBy :191-199 and processInBatchNoGroupBy :304-310
+ * end the same way), after `having` and before the OutputRateLimiter. It runs once per selector output chunk —
+ * one flush of sh_out, for every window family — on the rows that survived `having`:
+ *  - orderEventChunk (:452-483): the chunk is cut into maximal runs of consecutive rows of one type (CURRENT /
+ *    EXPIRED); each run is sorted on its own, stably (List.sort), and keeps its place. With current-only or
+ *    expired-only output a flush is one run; an `insert all events` flush whose types alternate on every row
+ *    comes out unchanged;
+ *  - OrderByEventComparator.compare (core/query/selector/OrderByEventComparator.java:63-117), term by term: two
+ *    non-null values by Integer / Long / Float / Double / Boolean.compareTo (Double: -0.0 < 0.0, every NaN equal
+ *    and above +Infinity; Boolean: false < true), negated for `desc`; exactly one null: the non-null row first,
+ *    for asc and desc alike (nulls are last, never inverted); both null or equal: the next term decides; all
+ *    terms equal: the chunk's earlier row stays first;
+ *  - offsetEventChunk (:502-519): the chunk's first `offset` rows are removed;
+ *  - limitEventChunk (:485-500): the test is `(limit > count) && (CURRENT && currentOn) || (EXPIRED && expiredOn)`
+ *    and `&&` binds first, so an EXPIRED row is always kept and counted and a CURRENT row only while fewer than
+ *    `limit` rows were kept: the row at position p after the offset is kept iff EXPIRED or p < limit (`limit 0`
+ *    removes every CURRENT row and keeps the EXPIRED ones);
+ *  - a chunk that keeps no row gives no flush (OutputRateLimiter.sendToCallBacks :89-105); the others keep their clocks;
+ *  - aggregators without group-by (processInBatchNoGroupBy, for every window family: execute :140-159): the
+ *    chunk's one row is kept iff offset is unset or 0 and limit is unset or > 0; there is no ordering.
+ * A term names a group-by column (SH_ORD_KEY, its number) or an aggregate (SH_ORD_AGG, its number; a float min /
+ * max, reported widened to double, orders as the float does); desc != 0 is `desc`; pad is ignored. n_terms 0..4;
+ * limit / offset -1 = not given. The terms are copied. Set once, before the first push (SH_ERR_STATE later or
+ * twice).
+ * SH_ERR_INVALID: a term's kind or number out of range, more than 4 terms, limit or offset below -1 (setLimit /
+ * setOffset :436-450 refuse negative values), nothing to do (no term, limit and offset both -1).
+ * SH_ERR_UNSUPPORTED, the message naming the shape (the query then stays on the CPU): a term on a string
+ * (SH_T_STRID) group key (String.compareTo needs the text), any term on a pass-through query without aggregators
+ * (`select *`: its order reads a stream attribute of the event; limit and offset alone run there), a partitioned
+ * query (partition_col >= 0), a group-by the library interns (wide keys), a sharded query's owner or an
+ * aggregation root, no window. On a live query an order and sh_query_set_ext_replace_ts refuse each other in
+ * either order. Everything else runs: the three batch windows, plain or with stream.current.event, time,
+ * externalTime and length; current / expired / all-events output; with `having`, an externalTimeBatch timeout and
+ * the output rate limiters (which see the ordered, cut rows); through sh_push, sh_push_device, staged pushes and
+ * sh_advance_time. An ordered query always gets the full host flush arrays (as a having or rate-limited query
+ * does): sh_query_set_compact_flushes / sh_query_set_device_flushes are ignored for it; the row arrays of
+ * sh_push_device stay on the device. The step keeps no state: a snapshot neither stores nor fingerprints the
+ * spec, and the caller sets it again on the new query before sh_query_restore.
+ * Both entry points were added without a change of SH_ABI_VERSION or of any struct: a caller detects them by
+ * symbol lookup (dlsym / SymbolLookup). */
+#define SH_ORD_KEY 0 /* index = number of the group-by column */
+#define SH_ORD_AGG 1 /* index = number of the aggregate       */
+typedef struct {
+    int32_t kind, index, desc, pad;
+} sh_order_term;
+int sh_query_set_order(sh_query* q, const sh_order_term* terms, int32_t n_terms, int64_t limit, int64_t offset);
+/* The verdict sh_query_set_order would give on a query created from `desc`, without a context or a GPU (the
+ * same validation code): the shim calls it at parse time to decide whether the query goes to the GPU. */
+int sh_order_check(const sh_query_desc* desc, const sh_order_term* terms, int32_t n_terms, int64_t limit,
+                   int64_t offset);
+
 /* externalTimeBatch's fourth parameter, the scheduler timeout in milliseconds
  * (ExternalTimeBatchWindowProcessor.java:196-207, `externalTimeBatch(ts, 1 sec, 0, 6 sec)`): when the
  * playback clock passes the last scheduled time (clock of the window's first event, of every batch

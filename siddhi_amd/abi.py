@@ -43,6 +43,13 @@ class FilterOp(C.Structure):
                 ("ival", C.c_int64), ("dval", C.c_double)]
 
 
+ORD_KEY, ORD_AGG = 0, 1  # kinds of an order-by term (sh_query_set_order)
+
+
+class OrderTerm(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("index", C.c_int32), ("desc", C.c_int32), ("pad", C.c_int32)]
+
+
 class AggSpec(C.Structure):
     _fields_ = [("fn", C.c_int32), ("col", C.c_int32)]
 
@@ -206,6 +213,20 @@ def compile_having(spec, expr) -> List[FilterOp]:
     return ops
 
 
+def compile_order(order_by) -> List[OrderTerm]:
+    """The terms of sh_query_set_order from [("agg", 1, "desc"), ("key", 0, "asc"), ...]: ("agg", i[, order]) is
+    aggregate number i of the query's aggs, ("key", i[, order]) its group-by column number i; the order is
+    "asc" (the default) or "desc". The library checks the numbers against the descriptor."""
+    terms: List[OrderTerm] = []
+    for term in order_by or ():
+        kind, index = term[0], term[1]
+        order = term[2] if len(term) > 2 else "asc"
+        if kind not in ("key", "agg") or order not in ("asc", "desc"):
+            raise ValueError(f"bad order-by term {term!r}")
+        terms.append(OrderTerm(kind=ORD_KEY if kind == "key" else ORD_AGG, index=int(index), desc=int(order == "desc")))
+    return terms
+
+
 @dataclass
 class QuerySpec:
     """`from S[filter]#window.kind(param...) select group..., aggs... group by group... insert ...`"""
@@ -229,7 +250,13 @@ class QuerySpec:
     replace_ts: bool = False           # externalTimeBatch(..., timeout, true): replaceTimestampWithBatchEndTime
     having: object = None              # `having` condition (compile_having syntax); batch windows with current
                                        # output, lengthBatch(L, true) / timeBatch(T, true) with any output
+    order_by: Optional[Sequence[tuple]] = None  # `order by` terms (compile_order syntax)
+    limit: Optional[int] = None        # `limit n` (None: not given)
+    offset: Optional[int] = None       # `offset n` (None: not given)
     _keep: list = field(default_factory=list, repr=False)
+
+    def has_order(self) -> bool:
+        return bool(self.order_by) or self.limit is not None or self.offset is not None
 
     def desc(self) -> QueryDesc:
         d = QueryDesc()
@@ -467,6 +494,9 @@ def setup_lib_prototypes(lib, prefix: str):
     if hasattr(lib, "sh_query_set_having"):  # (added without an ABI version change: found by symbol lookup)
         lib.sh_query_set_having.argtypes = [C.c_void_p, P(FilterOp), C.c_int32]
         lib.sh_having_check.argtypes = [P(QueryDesc), P(FilterOp), C.c_int32]
+    if hasattr(lib, "sh_query_set_order"):  # (likewise)
+        lib.sh_query_set_order.argtypes = [C.c_void_p, P(OrderTerm), C.c_int32, C.c_int64, C.c_int64]
+        lib.sh_order_check.argtypes = [P(QueryDesc), P(OrderTerm), C.c_int32, C.c_int64, C.c_int64]
     lib.sh_query_rep_ts_attr.argtypes = [C.c_void_p, P(P(C.c_int64)), P(C.c_int64)]
     lib.sh_aggregation_timing.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sh_shard_flush_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -515,7 +545,7 @@ ABI_SYMBOLS = [
     "sh_aggregation_shard_create", "sh_aggregation_stats", "sh_stage", "sh_push_staged", "sh_ingest_stats",
     "sh_aggregation_find", "sh_aggregation_snapshot", "sh_aggregation_restore", "sh_query_set_output_rate", "sh_query_set_ext_timeout", "sh_query_set_ext_replace_ts", "sh_query_set_compact_flushes", "sh_query_set_device_flushes", "sh_query_rep_ts_attr", "sh_aggregation_timing", "sh_shard_flush_windows",
     "sh_shard_snapshot", "sh_shard_restore", "sh_query_set_strings", "sh_rate_apply_merged",
-    "sh_query_set_having", "sh_having_check",
+    "sh_query_set_having", "sh_having_check", "sh_query_set_order", "sh_order_check",
 ]
 
 

@@ -236,6 +236,8 @@ Tuning Tuning::from_env() {
     t.pl_sort = !getenv("SH_PL_SORT") || on("SH_PL_SORT");
     if (getenv("SH_AGG_BAND_ROWS")) t.agg_band_rows = atoi(getenv("SH_AGG_BAND_ROWS"));
     t.slx_wave = !getenv("SH_SLX_WAVE") || on("SH_SLX_WAVE");
+    if (getenv("SH_ORD_BLOCK_MAX"))
+        t.ord_block_max = std::min(shd::kOrdBlockRows, std::max(0, atoi(getenv("SH_ORD_BLOCK_MAX"))));
     // a large push's independent small kernels beside the big passes; SH_SIDE_STREAM=0: one stream
     t.side_stream = !getenv("SH_SIDE_STREAM") || on("SH_SIDE_STREAM");
     // the multisplit fold as a persistent grid; =0 puts back one workgroup per unit, for A/B runs and bisecting

@@ -14,6 +14,7 @@
 
 #include "sh_internal.h"
 #include "sh_having.h"
+#include "sh_order.h"
 
 struct sh_ctx {
     int device = 0;
@@ -245,7 +246,9 @@ struct SlidingImpl;
 // epoch bytes; unset: bytes where a push can have a mark per 32 closed events, run_closed),
 // SH_XCD_WINDOWS=0 (the persistent fold's units dealt round-robin over the XCDs instead of one contiguous
 // run each), SH_FLAG_EPOCH0=n (the first epoch byte, 1..255: a test reaches the
-// wrap in a few pushes)
+// wrap in a few pushes), SH_ORD_BLOCK_MAX=n (order by: the largest flush, in rows, of a call whose sort runs on
+// the block route, 0 .. 1024, default 256; 0 sends every call to the global radix route, 1024 every call the
+// block route can hold to it)
 struct Tuning {
     bool side_stream = true;
     bool fold_grid = true;
@@ -256,6 +259,9 @@ struct Tuning {
     bool pl_sort = true;   // partitioned lengthBatch keyed by the partition on the sorted lanes (lane 3)
     bool slx_wave = true;     // expired / all-events sliding replay with a wave per key (k_slx_wkey); SH_SLX_WAVE=0: a lane per key
     int agg_band_rows = 8;
+    // measured crossover on the MI355X: the block route wins up to 256 rows per flush (0.148 vs 0.287 ms per call
+    // of 2^18 rows), the radix passes from 512 (0.281 vs 0.355 ms): DESIGN.md §6, profiles/order_limit_bench.json
+    int ord_block_max = 256;
     static Tuning from_env();
 };
 
@@ -326,6 +332,17 @@ struct sh_query {
     DevBuf fl_dev;
     // sh_query_set_having: the program run_closed and sc_rows evaluate per event (sh_having.h)
     HavingState hv;
+    // sh_query_set_order: `order by` / `limit` / `offset` over a call's finished rows (sh_order.cpp). The spec
+    // is configuration; the buffers are scratch of one call and its result, nothing is carried across calls
+    struct Order {
+        bool on = false;
+        shd::OrdSpec spec{};
+        DevBuf foff, perm, perm2, head, img, nul, key, key2, sort_tmp, flag, pre, tmp, cnt;
+        DevBuf o_ts, o_exp, o_rep, o_keys, o_vals, o_nulls;  // kept rows
+        PinnedVec<int64_t> flush_offsets{0}, flush_clock;
+        PinnedVec<uint32_t> h_cnt;
+        sh_out dev_out{};
+    } ord;
     std::vector<std::pair<int64_t, int64_t>> xr_starts;
     std::vector<int64_t> xr_rep, xr_vals;
     bool xt_Lvalid = false;
@@ -554,6 +571,9 @@ int xout_finish(sh_query* q, bool host_out, const sh_out** out);
 // output rate limiting over a call's device output (sh_rate.cpp); flush_dev: the input's flush
 // arrays are device memory (sliding windows)
 int rate_apply(sh_query* q, const sh_out* in, bool flush_dev, bool host_out, const sh_out** out);
+// order by / limit / offset over a call's device output, in front of the limiter (sh_order.cpp); the input's
+// flush arrays are host memory
+int order_apply(sh_query* q, const sh_out* in, bool host_out, const sh_out** out);
 
 // the flush layout a batch-window call fills: the host output's, or the device output's (host arrays too)
 struct FlushVecs {

@@ -1023,7 +1023,7 @@ static int pending_to_front(sh_query* q, int64_t lo, int64_t n) {
 // (or whose timestamps decrease) is reported back untouched and runs through the full pipeline.
 bool query_small_eligible(const sh_query* q, int64_t N) {
     if (N <= 0 || N > kSmallMax || q->kind != 0 || q->xmode || q->d.stream_current || q->partitioned || q->given ||
-        q->rate.kind != SH_RATE_NONE || q->ap.n == 0)
+        q->rate.kind != SH_RATE_NONE || q->ord.on || q->ap.n == 0)
         return false;
     const int w = q->d.window;
     return w == SH_WIN_LENGTH_BATCH || (w == SH_WIN_TIME_BATCH && q->e0_valid && q->clock_valid);
@@ -1804,6 +1804,7 @@ extern "C" int sh_query_set_ext_replace_ts(sh_query* q, int32_t on) {
         return sh_fail(SH_ERR_INVALID, "sh_query_set_ext_replace_ts: set it before the first push");
     if (!on) { q->xt_replace = false; return SH_OK; }
     if (q->hv.on) return sh_fail(SH_ERR_UNSUPPORTED, "replaceTimestampWithBatchEndTime with a having program");
+    if (q->ord.on) return sh_fail(SH_ERR_UNSUPPORTED, "replaceTimestampWithBatchEndTime with order by / limit");
     // unpartitioned, or partitioned on the sorted partition lanes (lane 3), whose rows carry the batch end
     const bool lanes = q->kind == 1 && q->d.partition_col >= 0 && q->sl && plane_is_sorted_lane(q);
     if ((q->kind != 0 && !lanes) || (q->d.partition_col >= 0 && !lanes) || q->given || q->internal_keys)
@@ -1840,11 +1841,34 @@ static int push_any(sh_query* q, const sh_batch* dev, bool host_out, const sh_ou
     return rep_attr_finish(q, *out, host_out);
 }
 
+// An ordered query's window always leaves the full flush layout in host memory (order_apply reads it):
+// the compact and the device layouts are switched off while its call runs.
+struct FullFlushes {
+    sh_query* q;
+    bool compact, device;
+    explicit FullFlushes(sh_query* q_) : q(q_), compact(q_->compact_flushes), device(q_->device_flushes) {
+        if (q->ord.on) q->compact_flushes = q->device_flushes = false;
+    }
+    ~FullFlushes() { q->compact_flushes = compact; q->device_flushes = device; }
+    FullFlushes(const FullFlushes&) = delete;
+    FullFlushes& operator=(const FullFlushes&) = delete;
+};
+
+// what follows the selector's rows: order by / limit / offset (QuerySelector.java:355-370), then the
+// output rate limiter. *out: the call's device output with its flush layout in host memory
+static int after_selector(sh_query* q, bool host_out, const sh_out** out) {
+    const bool rate = q->rate.kind != SH_RATE_NONE;
+    if (q->ord.on) RCHK(order_apply(q, *out, rate ? false : host_out, out));
+    if (rate) return rate_apply(q, *out, false, host_out, out);  // (flush layout in host memory, sliding_output)
+    return SH_OK;
+}
+
 static int push_any_core(sh_query* q, const sh_batch* dev, bool host_out, const sh_out** out) {
-    if (q->rate.kind != SH_RATE_NONE) {
+    if (q->rate.kind != SH_RATE_NONE || q->ord.on) {
         const bool sl = q->kind == 1;
+        FullFlushes _ff(q);
         RCHK(sl ? sliding_push(q, dev, false, out) : push_core(q, dev, false, out));
-        return rate_apply(q, *out, false, host_out, out);  // (flush layout in host memory, sliding_output)
+        return after_selector(q, host_out, out);
     }
     if (q->kind == 1) return sliding_push(q, dev, host_out, out);
     return push_core(q, dev, host_out, out);
@@ -2010,14 +2034,16 @@ static int advance_any(sh_query* q, int64_t now, const sh_out** out) {
         }
         return wide_finish(q, true, out);
     }
+    const bool after = q->rate.kind != SH_RATE_NONE || q->ord.on;
+    FullFlushes _ff(q);
     if (q->kind == 1) {
-        if (q->rate.kind == SH_RATE_NONE) return sliding_advance(q, now, out, true);
+        if (!after) return sliding_advance(q, now, out, true);
         RCHK(sliding_advance(q, now, out, false));  // the TIMER chunks' rows reach the limiter too
-        return rate_apply(q, *out, false, true, out);
+        return after_selector(q, true, out);
     }
-    if (q->rate.kind != SH_RATE_NONE) {
+    if (after) {
         RCHK(advance_core(q, now, false, out));
-        return rate_apply(q, *out, false, true, out);
+        return after_selector(q, true, out);
     }
     return advance_core(q, now, true, out);
 }

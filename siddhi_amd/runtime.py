@@ -94,6 +94,32 @@ def having_check(spec: abi.QuerySpec, expr=None) -> None:
     _check(lib().sh_having_check(C.byref(d), arr, len(ops)))
 
 
+def _order_args(spec: abi.QuerySpec, order_by="spec", limit="spec", offset="spec"):
+    order_by = spec.order_by if order_by == "spec" else order_by
+    limit = spec.limit if limit == "spec" else limit
+    offset = spec.offset if offset == "spec" else offset
+    terms = abi.compile_order(order_by)
+    arr = (abi.OrderTerm * max(1, len(terms)))(*terms)
+    return arr, len(terms), -1 if limit is None else int(limit), -1 if offset is None else int(offset)
+
+
+def order_check(spec: abi.QuerySpec, order_by="spec", limit="spec", offset="spec") -> None:
+    """sh_order_check: raises SiddhiError with the library's verdict (SH_ERR_INVALID: malformed spec,
+    SH_ERR_UNSUPPORTED: a shape that stays on the CPU) unless `spec` with its order_by / limit / offset (or the
+    ones given) runs on the GPU. Needs neither a context nor a GPU: what the shim calls at parse time."""
+    d = spec.desc()
+    arr, n, lim, off = _order_args(spec, order_by, limit, offset)
+    _check(lib().sh_order_check(C.byref(d), arr, n, lim, off))
+
+
+def order_debug_counts():
+    """(calls that entered the order / limit pass, ... that sorted on the block route, ... on the global route)
+    in this process: the library's debug hook, not part of the ABI."""
+    v = [C.c_int64(), C.c_int64(), C.c_int64()]
+    lib().sh_order_debug_counts(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
 class Context:
     def __init__(self, device: int = 0):
         self.h = C.c_void_p()
@@ -130,6 +156,8 @@ class GpuQuery:
                 _check(lib().sh_query_set_output_rate(self.h, abi.RATE_KINDS[spec.rate[0]], int(spec.rate[1])))
             if getattr(spec, "having", None) is not None:
                 self.set_having(spec.having)
+            if spec.has_order():
+                self.set_order()
             if spec.timeout:
                 _check(lib().sh_query_set_ext_timeout(self.h, int(spec.timeout)))
             if spec.replace_ts:
@@ -146,6 +174,12 @@ class GpuQuery:
         ops = abi.compile_having(self.spec, expr)
         arr = (abi.FilterOp * max(1, len(ops)))(*ops)
         _check(lib().sh_query_set_having(self.h, arr, len(ops)))
+
+    def set_order(self, order_by="spec", limit="spec", offset="spec"):
+        """sh_query_set_order: `order by` terms (abi.compile_order syntax), `limit` and `offset` (None: not
+        given) — the selector's last step, once per flush. Once, before the first push."""
+        arr, n, lim, off = _order_args(self.spec, order_by, limit, offset)
+        _check(lib().sh_query_set_order(self.h, arr, n, lim, off))
 
     def set_device_flushes(self, on: bool = True):
         """sh_query_set_device_flushes: sh_push_device leaves the flush layout in device memory too."""
