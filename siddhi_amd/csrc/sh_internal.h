@@ -251,7 +251,13 @@ void launch_aggregate(hipStream_t s, const Segment* segs, int nseg, int P, int l
                       // the multisplit kernel as a persistent grid with the next unit's records in flight
                       bool persistent = true,
                       // the persistent grid's workgroups of one XCD take one contiguous run of units
-                      bool xcd_units = true);
+                      bool xcd_units = true,
+                      // the multisplit kernel's order check: 0 a unit is folded without step (e), its list
+                      // verified on the way, and run again checked if that fails; 1 every unit checked at
+                      // once; 2 as 0 with every odd unit run again (SH_FOLD_CHECK)
+                      int fold_check = 0,
+                      // unit_rows has a reader behind this launch (dense rows need it for nothing else)
+                      bool rows_read = true);
 void launch_count_flags(hipStream_t s, const unsigned char* flags, i64 n, i64* blk_cnt, int nblk);
 void launch_scan_sum(hipStream_t s, i64* a, int n);
 // What a two-stream push's host reads after its final synchronisation, stored by k_bits_pre into

@@ -656,6 +656,18 @@ __global__ __launch_bounds__(kBlock) void k_aggregate_flat(const Segment* __rest
 // the 9 owner bits, a wave-private running count per owner), and after one workgroup scan per chunk
 // every record has its slot in its owner's list, in event order. The owner then folds its list.
 //
+// "In event order" rests on the LDS atomics of one round handing lanes that share an owner their ranks in
+// lane order, which gfx950 has always been seen to do (scripts/probe/lds_atomic_order.hip) but nothing
+// promises. A unit is therefore folded optimistically: step (e), the parallel check of the lists with its
+// insertion repair, is left out, and the owner compares every entry it folds with the one before (across
+// chunks too). The unit's state is in registers and its rows and first-event marks are written in the
+// epilogue only, so a unit whose workgroup found an entry out of order (one __syncthreads_or behind the last
+// chunk) is simply run again from its first chunk in checked form, step (e) included; nothing is undone.
+// `flags` (kOwn*) can check every unit at once, as before (SH_FOLD_CHECK=1), or run every odd unit a second
+// time (SH_FOLD_CHECK=2, which exercises that path). Only K == 1 is optimistic (kOptimistic below). With
+// dense rows whose push reads no rows per unit (kOwnRowsRead clear) the epilogue's row scan is left out as
+// well; that barrier then orders the LDS reuse.
+//
 // A workgroup is persistent. The units are (window, partition), window-major. With a grid that is a
 // multiple of 8 (workgroup b runs on XCD b & 7) each XCD takes one contiguous run of ceil(n_units / 8)
 // units, whole windows one after another, which its grid / 8 workgroups take in turn: workgroup b's i-th
@@ -669,6 +681,10 @@ __global__ __launch_bounds__(kBlock) void k_aggregate_flat(const Segment* __rest
 // the barriers up to the next decode. The LDS arrays are reused from chunk to chunk and unit to unit;
 // every reuse is behind a barrier (noted where it is not obvious).
 constexpr int kOwnT = 512;
+// `flags` of k_aggregate_own: dense rows; unit_rows has a reader; the order check's mode (neither bit:
+// optimistic with the check in the fold, SH_FOLD_CHECK=0; every unit checked at once, =1; optimistic with
+// every odd unit run again, =2)
+constexpr int kOwnDense = 1, kOwnRowsRead = 2, kOwnCheckAll = 4, kOwnCheckOdd = 8;
 template <int V, int K, int R, int F, u32 SIG, bool PACK>
 __global__ __launch_bounds__(kOwnT, 4) void k_aggregate_own(const i64* __restrict__ seg_off, int P, int logP,
                                                            int n_units, AggPlan ap, u64* rows, int RW,
@@ -677,7 +693,7 @@ __global__ __launch_bounds__(kOwnT, 4) void k_aggregate_own(const i64* __restric
                                                            const u32* __restrict__ rec_pos,
                                                            const u32* __restrict__ rec_idx,
                                                            const u64* __restrict__ rec_vals, i64 rec_cap, EvSrc es,
-                                                           int dense, int xcd_units) {
+                                                           int flags, int xcd_units) {
     constexpr int W = kOwnT / 64;
     constexpr int PW = 64 * R;   // records per wave and chunk
     constexpr int CH = kOwnT * R;
@@ -735,8 +751,19 @@ __global__ __launch_bounds__(kOwnT, 4) void k_aggregate_own(const i64* __restric
     bounds(unit_of(0), lo, hi, seg_lo);
     bounds(unit_of(1), nlo, nhi, nseg_lo);
     issue(lo, hi);
-    for (int ui = 0, unit; (unit = unit_of(ui)) < n_units; ui++) {
+    // A unit's first pass is optimistic unless kOwnCheckAll is set: it leaves out step (e) and the owner
+    // verifies its list's order while folding it. A pass that fails (kOwnCheckOdd: every odd unit's) is thrown
+    // away — its state is in registers, nothing of it has been stored — and the same unit is the loop's next
+    // turn, checked. With two keys per owner (K = 2) every unit takes the checked form at once: the optimistic
+    // pass measured slower there (C2 with int keys: the fold 391 -> 433 us), and the
+    // table-driven forms with 5 to 8 fields spilled more registers with the verdict carried through the unit.
+    constexpr bool kOptimistic = K == 1;
+    bool again = false;
+    for (int ui = 0, unit; (unit = unit_of(ui)) < n_units;) {
         const int p = unit & (P - 1);
+        const bool chk = !kOptimistic || again || (flags & kOwnCheckAll) != 0;
+        // (two keys per owner keep the scan: their rows are not staged, and compiled without it they spill)
+        const bool scan_rows = K > 1 || (flags & (kOwnDense | kOwnRowsRead)) != kOwnDense;
         SH_STAMP_UNIT_LDS(0, unit, 0);
         u32 cnt0 = 0, fst0 = 0, lst0 = 0, cnt1 = 0, fst1 = 0, lst1 = 0;
         i64 pf_ts = 0, pf_seq = 0;
@@ -744,6 +771,7 @@ __global__ __launch_bounds__(kOwnT, 4) void k_aggregate_own(const i64* __restric
         u64 f0[F], f1[F];
 #pragma unroll
         for (int j = 0; j < F; j++) { f0[j] = 0; f1[j] = 0; }
+        bool bad = false;
         i64 c0 = lo;
         do {
             const int n = (int)max((i64)0, min((i64)CH, hi - c0));
@@ -771,11 +799,13 @@ __global__ __launch_bounds__(kOwnT, 4) void k_aggregate_own(const i64* __restric
             if (n > 0) {
                 // (b) rank among the run's records of the same owner: a wave-private running count per
                 // owner, advanced by LDS atomics (the wave's rounds complete in program order; lanes of
-                // one round that share an owner get distinct ranks, in an order (e) restores).
+                // one round that share an owner get distinct ranks, in an order the fold verifies or (e)
+                // restores).
                 // (wcnt and lstart were last read in (d) and (e) of the chunk before: barriers since)
 #pragma unroll
                 for (int i = lane; i < kOwnT; i += 64) wcnt[w][i] = 0;
-                for (int i = t; i < CH / 32; i += kOwnT) lstart[i] = 0;
+                if (chk)
+                    for (int i = t; i < CH / 32; i += kOwnT) lstart[i] = 0;
 #pragma unroll
                 for (int j = 0; j < R; j++) {
                     if (li[j] == kNone) continue;
@@ -795,7 +825,7 @@ __global__ __launch_bounds__(kOwnT, 4) void k_aggregate_own(const i64* __restric
                 i64 all;
                 start = (u32)block_excl_scan_any((i64)tot, &all);
                 bstart[t] = start;
-                if (tot) atomicOr(&lstart[start >> 5], 1u << (start & 31));
+                if (chk && tot) atomicOr(&lstart[start >> 5], 1u << (start & 31));
                 __syncthreads();
                 // (d) every record into its owner's list (st_*: the fold of the chunk before and the row
                 // copy-out of the unit before read them ahead of the two barriers above)
@@ -814,11 +844,13 @@ __global__ __launch_bounds__(kOwnT, 4) void k_aggregate_own(const i64* __restric
                 // (e) the owner's list is in event order unless lanes of one round that shared the owner
                 // got their ranks out of lane order (never seen on gfx950:
                 // scripts/probe/lds_atomic_order.hip); checked in parallel over adjacent positions of one
-                // list, repaired by an insertion pass
-                bool bad = false;
-                for (int d = t; d + 1 < n; d += kOwnT)
-                    bad |= !((lstart[(d + 1) >> 5] >> ((d + 1) & 31)) & 1u) && st_idx[d + 1] < st_idx[d];
-                if (__syncthreads_or(bad) && tot > 1) {
+                // list, repaired by an insertion pass. Only a checked pass does this; an optimistic one has
+                // the owner compare each entry with the one before while it folds the list (below).
+                bool swapped = false;
+                if (chk)
+                    for (int d = t; d + 1 < n; d += kOwnT)
+                        swapped |= !((lstart[(d + 1) >> 5] >> ((d + 1) & 31)) & 1u) && st_idx[d + 1] < st_idx[d];
+                if (chk && __syncthreads_or(swapped) && tot > 1) {
                     u32 prev = st_idx[start];
                     for (u32 k = 1; k < tot; k++) {
                         const u32 e = st_idx[start + k];
@@ -874,8 +906,14 @@ __global__ __launch_bounds__(kOwnT, 4) void k_aggregate_own(const i64* __restric
                     for (int x = 0; x < V; x++) if (x < ap.n_vcols) v_nx[x] = (i64)st_v[x][start];
                     if (K > 1) hi_nx = st_hi[start];
                 }
+                // The order of the list, verified on the way (what an optimistic pass relies on): every entry
+                // is a later event than the one before it, the last entry of the chunk before included. The
+                // entry before is the key's last event so far, lst0 once cnt0 > 0 (K == 1: one key per owner). An
+                // empty list has none, so the combined index 0 is a valid first event. Entries are distinct
+                // events: "not later" fails.
                 for (u32 k = 0; k < tot; k++) {
                     const u32 e = e_nx;
+                    if (kOptimistic) bad |= cnt0 != 0 && e <= lst0;
                     i64 vv[V];
 #pragma unroll
                     for (int x = 0; x < V; x++) vv[x] = v_nx[x];
@@ -903,19 +941,37 @@ __global__ __launch_bounds__(kOwnT, 4) void k_aggregate_own(const i64* __restric
             c0 += CH;
         } while (c0 < hi);
         SH_STAMP_UNIT_LDS(0, unit, 5);
+        // One barrier stands here in every pass, and it is what orders the LDS reuse of the epilogue: the
+        // fold's reads of st_v before the row staging below, and the copy-out (st_v, has[]) of the unit
+        // before — which an empty unit follows with no chunk-loop barrier in between — before this unit's
+        // writes. In an optimistic pass it also carries the verdict, the same for the whole workgroup, and
+        // nothing of the unit — mark, staged row or stored row — precedes it.
+        if (chk) {
+            // (with the scan its two barriers do this: both precede every LDS write of the epilogue, and the
+            // scan's own words were last read before the barrier that ends the scan of (c))
+            if (!scan_rows) __syncthreads();
+        } else if (__syncthreads_or(bad || ((flags & kOwnCheckOdd) && (unit & 1)))) {
+            // Again, checked, from the unit's first chunk: its records over the next unit's prefetched ones
+            // (the last chunk issues those, and reads the bounds of the unit after, a second time).
+            again = true;
+            issue(lo, hi);
+            continue;
+        }
+        again = false;
         // one row per key with events, in the unit's own region of K * 512 row slots (no global counter:
         // a contended atomic on one address would serialise every workgroup of the launch)
         const int mine = (cnt0 > 0) + (K > 1 && cnt1 > 0);
-        i64 tot;
-        // The scan's two barriers, the second one behind its last LDS read, are also what orders the LDS
-        // reuse of the epilogue: the fold's reads of st_v before the row staging below, and the copy-out
-        // (st_v, has[]) of the unit before — which an empty unit follows with no chunk-loop barrier in
-        // between — before this unit's writes. A scan without its trailing barrier would need one here.
-        const i64 pre = block_excl_scan_any((i64)mine, &tot);
-        if (t == 0) unit_rows[unit] = (u32)tot;
+        // The rows of the unit, for the readers of unit_rows (the rank emission and the host's rows per
+        // segment); dense rows whose push takes its rows per segment from the bitmap's ranks have none, and
+        // need no `pre` either.
+        i64 tot = 0, pre = 0;
+        if (scan_rows) {
+            pre = block_excl_scan_any((i64)mine, &tot);
+            if (t == 0) unit_rows[unit] = (u32)tot;
+        }
         const u64 base = (u64)unit * (u64)(K * kOwnT);
         const bool staged = K == 1 && (size_t)kOwnT * RW * 8 <= sizeof(st_v);
-        if (dense) {
+        if (flags & kOwnDense) {
             // rows at their local key's slot of the unit (K * kOwnT rows, holes where a key had no
             // event): the emission finds a row from its first event's key slot, no rank scatter
             // (k_emit_gather)
@@ -973,6 +1029,7 @@ __global__ __launch_bounds__(kOwnT, 4) void k_aggregate_own(const i64* __restric
         SH_STAMP_UNIT_LDS(0, unit, 6);
         lo = nlo; hi = nhi; seg_lo = nseg_lo;
         nlo = nnlo; nhi = nnhi; nseg_lo = nnseg_lo;
+        ui++;
     }
 }
 
@@ -1003,7 +1060,7 @@ static int own_resident_grid() {
 template <int V, int K, int R, int F, u32 SIG, bool PACK>
 static void launch_own(hipStream_t s, int n_units, bool persistent, const i64* seg_off, int P, int logP, AggPlan ap,
                        u64* rows, int RW, u32* unit_rows, FirstMarks marks, const Segment* segs,
-                       const u32* rec_pos, const u32* rec_idx, const u64* rec_vals, i64 rec_cap, EvSrc es, int dense,
+                       const u32* rec_pos, const u32* rec_idx, const u64* rec_vals, i64 rec_cap, EvSrc es, int flags,
                        int xcd_units) {
     int grid = n_units;
     if (persistent && V == 1) {
@@ -1011,7 +1068,7 @@ static void launch_own(hipStream_t s, int n_units, bool persistent, const i64* s
         if (g > 0) grid = std::min(g, n_units);
     }
     hipLaunchKernelGGL((k_aggregate_own<V, K, R, F, SIG, PACK>), dim3(grid), dim3(kOwnT), 0, s, seg_off, P, logP, n_units,
-                       ap, rows, RW, unit_rows, marks, segs, rec_pos, rec_idx, rec_vals, rec_cap, es, dense, xcd_units);
+                       ap, rows, RW, unit_rows, marks, segs, rec_pos, rec_idx, rec_vals, rec_cap, es, flags, xcd_units);
 }
 
 int own_keys_per_thread(int NL) { return NL <= kOwnT ? 1 : 2; }
@@ -1022,8 +1079,11 @@ void launch_aggregate(hipStream_t s, const Segment* segs, int nseg, int P, int l
                       const u32* pend_pos, const u64* pend_vals, i64 pend_cap, const u32* new_pos, ColSet cols,
                       AggPlan ap, u64* rows, int RW, u32* unit_rows, FirstMarks marks,
                       const u32* rec_pos, const u32* rec_idx, const u64* rec_vals, i64 rec_cap, const i64* seg_off,
-                      bool pack, EvSrc es, bool dense_rows, bool persistent, bool xcd_units) {
-    const int dense = dense_rows ? 1 : 0, xcd = xcd_units ? 1 : 0;
+                      bool pack, EvSrc es, bool dense_rows, bool persistent, bool xcd_units, int fold_check,
+                      bool rows_read) {
+    const int xcd = xcd_units ? 1 : 0;
+    const int flags = (dense_rows ? kOwnDense : 0) | (rows_read ? kOwnRowsRead : 0) |
+                      (fold_check == 1 ? kOwnCheckAll : fold_check == 2 ? kOwnCheckOdd : 0);
     if (rec_idx) {  // multisplit records: thread-ownership kernel
         const int K = own_keys_per_thread(NL);
         const int F = ap.n_fields <= 2 ? 2 : ap.n_fields <= 4 ? 4 : 8;
@@ -1032,11 +1092,11 @@ void launch_aggregate(hipStream_t s, const Segment* segs, int nseg, int P, int l
         if (pack)                                                                                               \
             launch_own<VV, KK, RR, FF, SG, true>(s, nseg * P, persistent, seg_off, P, logP, ap, rows, RW,        \
                                                  unit_rows, marks, segs, rec_pos, rec_idx,                       \
-                                                 rec_vals, rec_cap, es, dense, xcd);                            \
+                                                 rec_vals, rec_cap, es, flags, xcd);                            \
         else                                                                                                    \
             launch_own<VV, KK, RR, FF, SG, false>(s, nseg * P, persistent, seg_off, P, logP, ap, rows, RW,       \
                                                   unit_rows, marks, segs, rec_pos, rec_idx,                      \
-                                                  rec_vals, rec_cap, es, dense, xcd);                           \
+                                                  rec_vals, rec_cap, es, flags, xcd);                           \
     } while (0)
 #define SH_AGG_OWN_F(VV, KK, RR)                          \
     do {                                                  \
@@ -1356,7 +1416,7 @@ void launch_emit_rows(hipStream_t s, const u64* rows, int RW, const u32* unit_ro
 
 size_t emit_stage_bytes(int nk, int na, int order, i64 n_rows) { return (size_t)stage_words(nk, na, order) * 8 * n_rows; }
 
-// One-pass emission for rows the fold left at their key's slot (dense rows, k_aggregate_own `dense`).
+// One-pass emission for rows the fold left at their key's slot (dense rows, k_aggregate_own `kOwnDense`).
 // A wave takes 512 events of the combined index space (16 words of the first-occurrence bitmap): every
 // set bit is a row's first event e. The lanes load the key slots of their 8 events (the slot column or
 // the dictionary ids, coalesced) and compact the set ones into LDS in event order; the chunk's rows have

@@ -246,6 +246,9 @@ Tuning Tuning::from_env() {
     // persistent fold's units; =0: the atomics on the bitmap and the round-robin order, for A/B runs
     t.first_flags = !getenv("SH_FIRST_FLAGS") ? -1 : on("SH_FIRST_FLAGS") ? 1 : 0;
     t.xcd_windows = !getenv("SH_XCD_WINDOWS") || on("SH_XCD_WINDOWS");
+    // the multisplit fold's order check: 0 in the fold, a failing unit run again; 1 step (e) for every unit, as
+    // before, for A/B runs and bisecting; 2 as 0 with every odd unit run again, which exercises that path
+    if (getenv("SH_FOLD_CHECK")) t.fold_check = std::min(2, std::max(0, atoi(getenv("SH_FOLD_CHECK"))));
     if (getenv("SH_FLAG_EPOCH0")) t.flag_epoch0 = std::min(255, std::max(1, atoi(getenv("SH_FLAG_EPOCH0"))));
     return t;
 }

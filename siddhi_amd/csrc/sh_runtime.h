@@ -245,7 +245,9 @@ struct SlidingImpl;
 // SH_FIRST_FLAGS=0 / 1 (the fold marks first events always with atomics on the zeroed bitmap / always with
 // epoch bytes; unset: bytes where a push can have a mark per 32 closed events, run_closed),
 // SH_XCD_WINDOWS=0 (the persistent fold's units dealt round-robin over the XCDs instead of one contiguous
-// run each), SH_FLAG_EPOCH0=n (the first epoch byte, 1..255: a test reaches the
+// run each), SH_FOLD_CHECK=1 / 2 (the multisplit fold checks every unit's list order in a step of its own, as
+// it did before the check moved into the fold / folds optimistically and runs every odd unit again, checked,
+// which the hardware's own ordering never asks for), SH_FLAG_EPOCH0=n (the first epoch byte, 1..255: a test reaches the
 // wrap in a few pushes), SH_ORD_BLOCK_MAX=n (order by: the largest flush, in rows, of a call whose sort runs on
 // the block route, 0 .. 1024, default 256; 0 sends every call to the global radix route, 1024 every call the
 // block route can hold to it)
@@ -254,6 +256,7 @@ struct Tuning {
     bool fold_grid = true;
     int first_flags = -1;  // -1: chosen per push
     bool xcd_windows = true;
+    int fold_check = 0;    // 0: verified in the fold, 1: step (e) for every unit, 2: 0 with odd units run again
     int flag_epoch0 = 1;
     bool direct_pos = false, part_keys_1024 = false, no_async_small = false, sl_records_seq = false;
     bool pl_sort = true;   // partitioned lengthBatch keyed by the partition on the sorted lanes (lane 3)

@@ -651,9 +651,9 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
     RCHK(upload_segments(q, segs, s2));
     const Segment* dsegs = q->segs.as<Segment>();
     // (marks: the form this call took — epoch bytes or atomics — and the epoch last handed out)
-    SH_TRACE("run_closed nseg=%d closed_hi=%lld row_cap=%lld own=%d P=%d NL=%d ms_ready=%d marks=%s epoch=%d", nseg,
-             (long long)closed_hi, (long long)row_cap, (int)own, q->P, q->NL, (int)q->ms_ready,
-             use_flags ? "bytes" : "atomics", q->flag_epoch);
+    SH_TRACE("run_closed nseg=%d closed_hi=%lld row_cap=%lld own=%d P=%d NL=%d ms_ready=%d marks=%s epoch=%d "
+             "fold_check=%d", nseg, (long long)closed_hi, (long long)row_cap, (int)own, q->P, q->NL, (int)q->ms_ready,
+             use_flags ? "bytes" : "atomics", q->flag_epoch, q->tune.fold_check);
     if (own) {
         if (!q->ms_ready) RCHK(run_multisplit(q, closed_hi, b, false, long_seg));
         RCHK(q->seg_off.reserve((size_t)(nseg + 1) * q->P * 8, false));
@@ -671,6 +671,12 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
     // multisplit units leave every row at its key's slot and one pass emits them (k_emit_gather; the
     // round-4 rank scatter + column split remain for the other units)
     const bool gather = own;
+    // a two-stream push's tail: the rows per segment (as bitmap ranks) and the key table's control words
+    // are stored into h_tail by k_bits_pre, so no copy waits behind the emission (each was a blit kernel
+    // behind a 10-12 us gap). The other paths copy the rows per unit and the control words as before.
+    // (The rows per unit are then read by nobody — the gather emission finds a row from its key's slot,
+    // closed_finish takes rank differences — and the fold does not count them.)
+    const bool tail_direct = side && gather;
     HIPCHK(hipEventRecord(q->ev_agg0, s));
     launch_aggregate(s, dsegs, nseg, q->P, q->logP, q->NL, q->n_pend, q->pend_pos.as<u32>(), q->pend_vals.as<u64>(),
                      q->pend_cap, b ? q->new_pos.as<u32>() : nullptr, cs, q->ap, q->rows.as<u64>(), RW,
@@ -679,7 +685,7 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
                      q->rec_packed,
                      EvSrc{q->n_pend, q->pend_ts.as<int64_t>(), ts, q->pend_gidx.as<u64>(),
                            q->given && b ? q->given_gidx : nullptr, q->seq},
-                     gather, q->tune.fold_grid, q->tune.xcd_windows);
+                     gather, q->tune.fold_grid, q->tune.xcd_windows, q->tune.fold_check, !tail_direct);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(q->ev_agg1, s));
     // output columns sized for the row capacity; the emit kernels read the row count on the device
@@ -695,10 +701,6 @@ static int run_closed(sh_query* q, const std::vector<Segment>& segs, const std::
     RCHK(q->blk_cnt.reserve((nbt + 16) * 8, false));
     RCHK(q->word_pre.reserve((size_t)n_words * 8, false));
     if (!gather) RCHK(q->emit_stage.reserve(emit_stage_bytes(nk, na, q->given ? 1 : 0, cap), false));
-    // a two-stream push's tail: the rows per segment (as bitmap ranks) and the key table's control words
-    // are stored into h_tail by k_bits_pre, so no copy waits behind the emission (each was a blit kernel
-    // behind a 10-12 us gap). The other paths copy the rows per unit and the control words as before.
-    const bool tail_direct = side && gather;
     RCHK(q->h_tail.reserve(16 + (size_t)std::max<int64_t>(n_units, 2 * (int64_t)nseg) * 4));
     TailOut to{};
     if (tail_direct) {
