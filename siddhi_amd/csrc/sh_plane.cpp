@@ -81,16 +81,6 @@ int plane_create(sh_query* q) {
     return SH_OK;
 }
 
-// host copy of n i64 from the device
-static int d2h(sh_query* q, std::vector<int64_t>& v, const void* dev, int64_t n) {
-    v.resize((size_t)std::max<int64_t>(n, 0));
-    if (n > 0) {
-        HIPCHK(hipMemcpyAsync(v.data(), dev, (size_t)n * 8, hipMemcpyDeviceToHost, q->ctx->stream));
-        HIPCHK(hipStreamSynchronize(q->ctx->stream));
-    }
-    return SH_OK;
-}
-
 static int h2d(sh_query* q, DevBuf& b, const std::vector<int64_t>& v) {
     RCHK(b.reserve(std::max<size_t>(v.size(), 1) * 8, false));
     if (!v.empty()) HIPCHK(hipMemcpyAsync(b.p, v.data(), v.size() * 8, hipMemcpyHostToDevice, q->ctx->stream));
@@ -387,51 +377,27 @@ static int plane_run_group(sh_query* q, const sh_batch* b, int64_t now, bool hos
         return empty_out(q, out);
     }
     HIPCHK(hipEventRecord(q->ev_push0, st));
-    const int64_t cap = std::max<int64_t>(N, 1);
-    RCHK(s->rec_raw.reserve(cap * 4, false));
-    RCHK(s->rec_slot.reserve(cap * 4, false));
-    RCHK(s->rec_clock.reserve(cap * 8, false));
-    RCHK(s->rec_pm.reserve(cap * 8, false));
-    RCHK(s->rec_ts.reserve(cap * 8, false));
-    RCHK(s->rec_vals.reserve((size_t)V * cap * 8, false));
-    RCHK(s->slot_cnt.reserve(s->nslots * 4, false));
     RCHK(s->pg_prevcnt.reserve(s->nslots * 4, false));
     RCHK(s->pg_pendcnt.reserve(s->nslots * 4, false));
-    HIPCHK(hipMemsetAsync(s->slot_cnt.p, 0, s->nslots * 4, st));
     HIPCHK(hipMemsetAsync(s->pg_prevcnt.p, 0, s->nslots * 4, st));
     HIPCHK(hipMemsetAsync(s->pg_pendcnt.p, 0, s->nslots * 4, st));
-    SlRecords rec{s->rec_raw.as<u32>(), s->rec_slot.as<u32>(), s->rec_clock.as<int64_t>(), s->rec_pm.as<int64_t>(),
-                  s->rec_ts.as<int64_t>(), s->rec_vals.as<u64>(), cap};
-    ColSet cs{};
-    cs.n = q->d.n_cols;
-    for (int c = 0; c < q->d.n_cols; c++) { cs.type[c] = q->d.col_types[c]; cs.ptr[c] = b ? b->cols[c] : nullptr; }
-    const int nblk = (int)((N + kTile - 1) / kTile);
-    RCHK(s->blk_pass.reserve(nblk * 8, false));
-    RCHK(s->blk_tl.reserve(nblk * 8, false));
-    RCHK(s->blk_pm.reserve(nblk * 8, false));
-    WinParams wp{};
-    wp.kind = SH_WIN_TIME;  // the clock / pass-count prefix of the sliding path
-    wp.clock_valid = q->clock_valid;
-    wp.clock0 = q->clock;
-    wp.send_size = ss;
-    wp.N = N;
-    wp.rec_seq = q->tune.sl_records_seq;  // (the lane-strided records where they apply, as the sliding path)
-    const bool sorted_off = b && sl_records_seq_applies(q->fp, wp, q->ap);
+    // lane-strided records (every event passes): no per-slot counts; the partitions' offsets come from the
+    // slots sorted below, carried records included (k_counts_sorted; the LDS tables and atomics were 5.2 of
+    // plb's 20 ms)
+    RecOpts ro;
+    ro.V = V;
+    ro.base = s->pm;
+    ro.presort = true;
+    ro.sort = ro.need = false;
+    RecStage stg;
+    RCHK(records_launch(q, b, ro, &stg));
+    const SlRecords rec = stg.rec;
+    const ColSet& cs = stg.cs;
+    const bool sorted_off = stg.presorted;
     SlInfo info{};
     if (b) {
-        launch_sl_prefix(st, b->ts, cs, q->fp, wp, s->blk_pass.as<int64_t>(), s->blk_tl.as<int64_t>(),
-                         s->blk_pm.as<int64_t>(), nblk, s->info.as<SlInfo>());
-        // lane-strided records (every event passes): no per-slot counts; the partitions' offsets come from
-        // the sorted slots below (k_counts_sorted; the LDS tables and atomics were 5.2 of plb's 20 ms)
-        launch_sl_records(st, b->ts, cs, q->fp, wp, q->kp, q->kt.dev(), q->ap, s->blk_pass.as<int64_t>(),
-                          s->blk_tl.as<int64_t>(), s->blk_pm.as<int64_t>(), s->pm, rec,
-                          sorted_off ? nullptr : s->slot_cnt.as<u32>(), nblk);
         if (xt) launch_pl_slot_key(st, cs, q->kp, q->kt.dev(), N, s->pl_key.as<int64_t>());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(s->h_info, s->info.p, sizeof(SlInfo), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        RCHK(q->kt.check(st));
-        info = *s->h_info;
+        RCHK(records_wait(q, stg, &info));
     }
     const int64_t M = info.total_pass, n_old = s->pg_n, n = n_old + M;
     int64_t n_rows = 0, n_flushes = 0;
@@ -441,25 +407,8 @@ static int plane_run_group(sh_query* q, const sh_batch* b, int64_t now, bool hos
     bool xt_fire = false;
     if (xt) {
         if (b) {
-            const int64_t NS = ss > 0 ? (N + ss - 1) / ss : 1;
-            const int nbS = (int)((NS + kTile - 1) / kTile);
-            RCHK(s->x_sK.reserve(NS * 8, false));
-            RCHK(s->x_scb.reserve(NS * 8, false));
-            RCHK(s->x_slast.reserve(NS * 8, false));
-            RCHK(s->x_cK.reserve(NS * 8, false));
-            RCHK(s->x_cC.reserve(NS * 8, false));
-            RCHK(s->x_cS.reserve(NS * 8, false));
-            RCHK(s->x_blk.reserve((size_t)((NS + kTile - 1) / kTile + 2) * 8, false));
-            launch_slx_sends(st, b->ts, cs, q->fp, wp, s->blk_pass.as<int64_t>(), s->blk_tl.as<int64_t>(), nblk,
-                             s->x_sK.as<int64_t>(), s->x_scb.as<int64_t>(), s->x_slast.as<int64_t>());
-            launch_slx_compact(st, 0, nullptr, s->x_sK.as<int64_t>(), s->x_scb.as<int64_t>(), s->x_slast.as<int64_t>(),
-                               NS, s->x_blk.as<int64_t>(), s->x_cK.as<int64_t>(), s->x_cC.as<int64_t>(),
-                               s->x_cS.as<int64_t>());
-            HIPCHK(hipGetLastError());
             int64_t nC = 0;
-            RCHK(read_count(q, s->x_blk.as<int64_t>() + nbS, &nC));
-            RCHK(d2h(q, calls_s, s->x_cS.p, nC));
-            RCHK(d2h(q, calls_c, s->x_cC.p, nC));
+            RCHK(push_calls(q, b, stg, &nC, &calls_s, &calls_c, nullptr));
         } else if (!q->clock_valid || now >= q->clock) {
             calls_s.push_back(0);
             calls_c.push_back(now);
@@ -489,15 +438,7 @@ static int plane_run_group(sh_query* q, const sh_batch* b, int64_t now, bool hos
                          s->pg_pendcnt.as<u32>());
         HIPCHK(hipGetLastError());
         // ---- every partition's records in stream order
-        RCHK(s->ranks.reserve(n * 4, false));
-        RCHK(s->p_slot.reserve(n * 4, false));
-        size_t tb = 0;
-        if (sort_slot_ranks(nullptr, &tb, C.ps, nullptr, nullptr, n, s->nslots, st))
-            return sh_fail(SH_ERR_DEVICE, "radix sort sizing failed");
-        RCHK(s->sort_tmp.reserve(std::max<size_t>(tb, 16), false));
-        if (sort_slot_ranks(s->sort_tmp.p, &tb, C.ps, s->p_slot.as<u32>(), s->ranks.as<u32>(), n, s->nslots, st))
-            return sh_fail(SH_ERR_DEVICE, "radix sort failed");
-        RCHK(s->key_off.reserve((size_t)(s->nslots + 1) * 4, false));
+        RCHK(sort_keyed(q, C.ps, n));
         RCHK(s->tmp.reserve((size_t)((s->nslots + 1 + kTile - 1) / kTile + 16) * 8, false));
         if (sorted_off) launch_counts_sorted(st, s->p_slot.as<u32>(), n, s->slot_cnt.as<u32>());
         launch_slx_keyoff(st, s->slot_cnt.as<u32>(), s->nslots, s->key_off.as<u32>(), s->tmp.as<int64_t>());
@@ -520,14 +461,10 @@ static int plane_run_group(sh_query* q, const sh_batch* b, int64_t now, bool hos
             X = PgExt{s->pg_M.as<int64_t>(), s->pg_start.as<int64_t>(), s->pg_has.as<unsigned char>(),
                       s->pg_bopen.as<int64_t>(), q->d.has_start_time, q->d.ts_col, q->d.start_col, q->d.start_time,
                       q->d.window_param};
-            tb = 0;
-            if (launch_pg_ext_scan(st, s->ranks.as<u32>(), s->p_slot.as<u32>(), C, n, s->pg_xv.as<int64_t>(),
-                                   s->pg_ms.as<int64_t>(), nullptr, &tb))
-                return sh_fail(SH_ERR_DEVICE, "scan sizing failed");
-            RCHK(s->sort_tmp.reserve(std::max<size_t>(tb, 16), false));
-            if (launch_pg_ext_scan(st, s->ranks.as<u32>(), s->p_slot.as<u32>(), C, n, s->pg_xv.as<int64_t>(),
-                                   s->pg_ms.as<int64_t>(), s->sort_tmp.p, &tb))
-                return sh_fail(SH_ERR_DEVICE, "scan failed");
+            RCHK(with_sort_tmp(q, "scan", [&](void* tmp, size_t* tb) {
+                return launch_pg_ext_scan(st, s->ranks.as<u32>(), s->p_slot.as<u32>(), C, n, s->pg_xv.as<int64_t>(),
+                                          s->pg_ms.as<int64_t>(), tmp, tb);
+            }));
             if (xt) {
                 RCHK(s->xt_flag.reserve(n + 16, false));
                 launch_pg_xt_flags(st, s->key_off.as<u32>(), s->ranks.as<u32>(), s->pg_prevcnt.as<u32>(),
@@ -608,7 +545,6 @@ static int plane_run_group(sh_query* q, const sh_batch* b, int64_t now, bool hos
             RCHK(read_count(q, s->pg_cnt.as<int64_t>(), &n_e));
         }
         if (n_e > 0) {
-            tb = 0;
             // (current only: one entry per event; the timeout's entries are exactly n_e)
             const int64_t ne_sort = xt ? n_e : q->d.expired_on ? ne_cap : n;
             const unsigned sbits = xt ? (unsigned)(gbits + bits_for((int64_t)em.size() + 1)) : ebits;
@@ -616,23 +552,16 @@ static int plane_run_group(sh_query* q, const sh_batch* b, int64_t now, bool hos
             // the (chunk, group) order is the chunk order: the radix sort skips the group bits (stable: a
             // chunk's entries keep their order either way; the `none` key's chunk bits are all ones)
             const unsigned sbeg = (!xt && !q->group_other) ? (unsigned)gbits : 0u;
-            if (sort_u64_pairs_range(nullptr, &tb, s->pg_ekey.as<u64>(), nullptr, s->pg_eval.as<u32>(), nullptr, ne_sort,
-                                     sbeg, sbits, st))
-                return sh_fail(SH_ERR_DEVICE, "radix sort sizing failed");
-            RCHK(s->sort_tmp.reserve(std::max<size_t>(tb, 16), false));
-            if (sort_u64_pairs_range(s->sort_tmp.p, &tb, s->pg_ekey.as<u64>(), s->pg_ekey2.as<u64>(), s->pg_eval.as<u32>(),
-                                     s->pg_eval2.as<u32>(), ne_sort, sbeg, sbits, st))
-                return sh_fail(SH_ERR_DEVICE, "radix sort failed");
+            RCHK(with_sort_tmp(q, "radix sort", [&](void* tmp, size_t* tb) {
+                return sort_u64_pairs_range(tmp, tb, s->pg_ekey.as<u64>(), s->pg_ekey2.as<u64>(), s->pg_eval.as<u32>(),
+                                            s->pg_eval2.as<u32>(), ne_sort, sbeg, sbits, st);
+            }));
             // ---- segments = rows
             RCHK(s->pg_head.reserve(n_e + 16, false));
             RCHK(s->pg_seg.reserve(n_e * 8, false));
-            RCHK(s->x_blk.reserve((size_t)((n_e + kTile - 1) / kTile + 2) * 8, false));
             launch_pg_heads(st, s->pg_ekey2.as<u64>(), n_e, s->pg_head.as<unsigned char>());
-            launch_slx_compact(st, 1, s->pg_head.as<unsigned char>(), nullptr, nullptr, nullptr, n_e,
-                               s->x_blk.as<int64_t>(), nullptr, nullptr, s->pg_seg.as<int64_t>());
-            HIPCHK(hipGetLastError());
             int64_t n_seg = 0;
-            RCHK(read_count(q, s->x_blk.as<int64_t>() + (n_e + kTile - 1) / kTile, &n_seg));
+            RCHK(compact_flags(q, s->pg_head.as<unsigned char>(), n_e, s->pg_seg.as<int64_t>(), &n_seg));
             n_rows = sc ? M : n_seg;  // (stream.current: a row per event of the push, else one per segment)
             const int64_t rc = std::max<int64_t>(n_rows, 1);
             RCHK(s->xr_ts.reserve(rc * 8, false));
@@ -670,13 +599,10 @@ static int plane_run_group(sh_query* q, const sh_batch* b, int64_t now, bool hos
                 HIPCHK(hipEventRecord(q->ev_agg1, st));
                 // ---- rows in (chunk, first entry) order
                 const unsigned rbits = (unsigned)(32 + (xt ? bits_for((int64_t)em.size() + 1) : cbits));
-                tb = 0;
-                if (sort_u64_iota_bits(nullptr, &tb, s->pg_rkey.as<u64>(), nullptr, nullptr, n_rows, rbits, st))
-                    return sh_fail(SH_ERR_DEVICE, "radix sort sizing failed");
-                RCHK(s->sort_tmp.reserve(std::max<size_t>(tb, 16), false));
-                if (sort_u64_iota_bits(s->sort_tmp.p, &tb, s->pg_rkey.as<u64>(), s->pg_rkey2.as<u64>(),
-                                       s->pg_order.as<u32>(), n_rows, rbits, st))
-                    return sh_fail(SH_ERR_DEVICE, "radix sort failed");
+                RCHK(with_sort_tmp(q, "radix sort", [&](void* tmp, size_t* tb) {
+                    return sort_u64_iota_bits(tmp, tb, s->pg_rkey.as<u64>(), s->pg_rkey2.as<u64>(), s->pg_order.as<u32>(),
+                                              n_rows, rbits, st);
+                }));
             }
             RCHK(s->out_ts.reserve(rc * 8, false));
             RCHK(s->out_keys.reserve((size_t)std::max(1, q->gkp.n) * rc * 8, false));
@@ -735,33 +661,19 @@ static int plane_run_group(sh_query* q, const sh_batch* b, int64_t now, bool hos
         }
         // ---- carry the open batches (and the last completed ones) in stream order
         RCHK(s->x_idx.reserve(n * 8, false));
-        RCHK(s->x_blk.reserve((size_t)((n + kTile - 1) / kTile + 2) * 8, false));
-        launch_slx_compact(st, 1, s->pg_keep.as<unsigned char>(), nullptr, nullptr, nullptr, n, s->x_blk.as<int64_t>(),
-                           nullptr, nullptr, s->x_idx.as<int64_t>());
-        HIPCHK(hipGetLastError());
         int64_t n_keep = 0;
-        RCHK(read_count(q, s->x_blk.as<int64_t>() + (n + kTile - 1) / kTile, &n_keep));
+        RCHK(compact_flags(q, s->pg_keep.as<unsigned char>(), n, s->x_idx.as<int64_t>(), &n_keep));
         RCHK(pg_grow(q, s->pg[1], s->pg[1], std::max<int64_t>(n_keep, 1), 0, V));
         launch_pg_gather(st, s->x_idx.as<int64_t>(), n_keep, s->pg_keep.as<unsigned char>(), C, s->pg[1].view(), V);
         HIPCHK(hipGetLastError());
         std::swap(s->pg[0], s->pg[1]);
         s->pg_n = n_keep;
     }
-    q->seq += N;
-    if (b) {
-        q->clock = q->clock_valid ? std::max(q->clock, info.max_tl) : info.max_tl;
-        q->clock_valid = true;
-    } else if (!q->clock_valid || now >= q->clock) {
+    if (!b && (!q->clock_valid || now >= q->clock)) {
         q->clock = now;
         q->clock_valid = true;
     }
-    q->stats.events = N;
-    HIPCHK(hipEventRecord(q->ev_push1, st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, q->ev_push0, q->ev_push1);
-    q->stats.push_ms = ms;
-    q->stats.main_kernel_bytes = M * (int64_t)(16 + 8 * V) + n_rows * (int64_t)(8 + 8 * na);
+    RCHK(push_done(q, b, info, M * (int64_t)(16 + 8 * V) + n_rows * (int64_t)(8 + 8 * na)));
     return sliding_output(q, n_rows, n_flushes, false, host_out, out);
 }
 
@@ -822,70 +734,30 @@ static int plane_run_tbsc(sh_query* q, const sh_batch* b, int64_t now, bool host
     const int V = std::max(1, q->ap.n_vcols), na = q->ap.n;
     if (N >= (int64_t)0x3FFFFFF0ll) return sh_fail(SH_ERR_INVALID, "push larger than 1G events");
     HIPCHK(hipEventRecord(q->ev_push0, st));
-    const int64_t cap = std::max<int64_t>(N, 1);
-    RCHK(s->rec_raw.reserve(cap * 4, false));
-    RCHK(s->rec_slot.reserve(cap * 4, false));
-    RCHK(s->rec_clock.reserve(cap * 8, false));
-    RCHK(s->rec_pm.reserve(cap * 8, false));
-    RCHK(s->rec_ts.reserve(cap * 8, false));
-    RCHK(s->rec_vals.reserve((size_t)V * cap * 8, false));
-    RCHK(s->slot_cnt.reserve(s->nslots * 4, false));
-    HIPCHK(hipMemsetAsync(s->slot_cnt.p, 0, s->nslots * 4, st));
-    SlRecords rec{s->rec_raw.as<u32>(), s->rec_slot.as<u32>(), s->rec_clock.as<int64_t>(), s->rec_pm.as<int64_t>(),
-                  s->rec_ts.as<int64_t>(), s->rec_vals.as<u64>(), cap};
-    ColSet cs{};
-    cs.n = q->d.n_cols;
-    for (int c = 0; c < q->d.n_cols; c++) { cs.type[c] = q->d.col_types[c]; cs.ptr[c] = b->cols[c]; }
-    const int nblk = (int)((N + kTile - 1) / kTile);
-    RCHK(s->blk_pass.reserve(nblk * 8, false));
-    RCHK(s->blk_tl.reserve(nblk * 8, false));
-    RCHK(s->blk_pm.reserve(nblk * 8, false));
-    WinParams wp{};
-    wp.kind = SH_WIN_TIME;  // the clock / pass-count prefix of the sliding path
-    wp.clock_valid = q->clock_valid;
-    wp.clock0 = q->clock;
-    wp.send_size = ss;
-    wp.N = N;
-    wp.rec_seq = q->tune.sl_records_seq;
-    launch_sl_prefix(st, b->ts, cs, q->fp, wp, s->blk_pass.as<int64_t>(), s->blk_tl.as<int64_t>(),
-                     s->blk_pm.as<int64_t>(), nblk, s->info.as<SlInfo>());
-    launch_sl_records(st, b->ts, cs, q->fp, wp, q->kp, q->kt.dev(), q->ap, s->blk_pass.as<int64_t>(),
-                      s->blk_tl.as<int64_t>(), s->blk_pm.as<int64_t>(), s->pm, rec, s->slot_cnt.as<u32>(), nblk);
+    // (every slot counted by the records kernel, no ring need: the states are per (partition, group))
+    RecOpts ro;
+    ro.V = V;
+    ro.base = s->pm;
+    ro.need = false;
+    RecStage stg;
+    RCHK(records_launch(q, b, ro, &stg));
+    const SlRecords rec = stg.rec;
+    const ColSet& cs = stg.cs;
+    const int64_t cap = stg.cap;
     launch_pl_slot_key(st, cs, q->kp, q->kt.dev(), N, s->pl_key.as<int64_t>());
     // partition runs over every event (the receiver cuts a send at key changes, before the filter)
     RCHK(s->tb_start.reserve(cap + 16, false));
     RCHK(s->tb_run.reserve(cap * 8, false));
-    RCHK(s->tb_blk.reserve((size_t)(nblk + 16) * 8, false));
+    RCHK(s->tb_blk.reserve((size_t)(stg.nblk + 16) * 8, false));
     launch_pl_runs(st, cs, q->d.partition_col, N, ss, s->tb_start.as<unsigned char>(), s->tb_blk.as<int64_t>(),
                    s->tb_run.as<int64_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s->h_info, s->info.p, sizeof(SlInfo), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    RCHK(q->kt.check(st));
-    const SlInfo info = *s->h_info;
+    SlInfo info{};
+    RCHK(records_wait(q, stg, &info));
     const int64_t M = info.total_pass;
     // the push's calls (a send whose last event does not move the clock calls nobody)
     std::vector<int64_t> calls_s, calls_c;
-    {
-        const int64_t NS = ss > 0 ? (N + ss - 1) / ss : 1;
-        const int nbS = (int)((NS + kTile - 1) / kTile);
-        RCHK(s->x_sK.reserve(NS * 8, false));
-        RCHK(s->x_scb.reserve(NS * 8, false));
-        RCHK(s->x_slast.reserve(NS * 8, false));
-        RCHK(s->x_cK.reserve(NS * 8, false));
-        RCHK(s->x_cC.reserve(NS * 8, false));
-        RCHK(s->x_cS.reserve(NS * 8, false));
-        RCHK(s->x_blk.reserve((size_t)((std::max(NS, M) + kTile - 1) / kTile + 2) * 8, false));
-        launch_slx_sends(st, b->ts, cs, q->fp, wp, s->blk_pass.as<int64_t>(), s->blk_tl.as<int64_t>(), nblk,
-                         s->x_sK.as<int64_t>(), s->x_scb.as<int64_t>(), s->x_slast.as<int64_t>());
-        launch_slx_compact(st, 0, nullptr, s->x_sK.as<int64_t>(), s->x_scb.as<int64_t>(), s->x_slast.as<int64_t>(), NS,
-                           s->x_blk.as<int64_t>(), s->x_cK.as<int64_t>(), s->x_cC.as<int64_t>(), s->x_cS.as<int64_t>());
-        HIPCHK(hipGetLastError());
-        int64_t nC = 0;
-        RCHK(read_count(q, s->x_blk.as<int64_t>() + nbS, &nC));
-        RCHK(d2h(q, calls_s, s->x_cS.p, nC));
-        RCHK(d2h(q, calls_c, s->x_cC.p, nC));
-    }
+    int64_t nC = 0;
+    RCHK(push_calls(q, b, stg, &nC, &calls_s, &calls_c, nullptr));
     // the chunks (partition runs with passing events) and their partition, send and clock
     int64_t nch = 0;
     std::vector<int64_t> ch_send, ch_clk, ch_bid;
@@ -894,10 +766,7 @@ static int plane_run_tbsc(sh_query* q, const sh_batch* b, int64_t now, bool host
         RCHK(s->tb_flag.reserve(M + 16, false));
         RCHK(s->tb_first.reserve(M * 8, false));
         launch_tb_chunk_flags(st, rec, M, s->tb_run.as<int64_t>(), s->tb_flag.as<unsigned char>());
-        launch_slx_compact(st, 1, s->tb_flag.as<unsigned char>(), nullptr, nullptr, nullptr, M, s->x_blk.as<int64_t>(),
-                           nullptr, nullptr, s->tb_first.as<int64_t>());
-        HIPCHK(hipGetLastError());
-        RCHK(read_count(q, s->x_blk.as<int64_t>() + (M + kTile - 1) / kTile, &nch));
+        RCHK(compact_flags(q, s->tb_flag.as<unsigned char>(), M, s->tb_first.as<int64_t>(), &nch));
         RCHK(s->tb_cslot.reserve(nch * 4 + 16, false));
         RCHK(s->tb_csend.reserve(nch * 8 + 16, false));
         RCHK(s->tb_cclk.reserve(nch * 8 + 16, false));
@@ -951,21 +820,14 @@ static int plane_run_tbsc(sh_query* q, const sh_batch* b, int64_t now, bool host
         const int64_t nst = (int64_t)q->pgkt.size_ + 1;
         RCHK(s->tb_skey.reserve(M * 4, false));
         RCHK(s->tb_sidx.reserve(M * 4, false));
-        size_t tb = 0;
-        if (sort_slot_ranks(nullptr, &tb, s->tb_pair.as<u32>(), nullptr, nullptr, M, nst, st))
-            return sh_fail(SH_ERR_DEVICE, "radix sort sizing failed");
-        RCHK(s->sort_tmp.reserve(std::max<size_t>(tb, 16), false));
-        if (sort_slot_ranks(s->sort_tmp.p, &tb, s->tb_pair.as<u32>(), s->tb_skey.as<u32>(), s->tb_sidx.as<u32>(), M, nst,
-                            st))
-            return sh_fail(SH_ERR_DEVICE, "radix sort failed");
+        RCHK(with_sort_tmp(q, "radix sort", [&](void* tmp, size_t* tb) {
+            return sort_slot_ranks(tmp, tb, s->tb_pair.as<u32>(), s->tb_skey.as<u32>(), s->tb_sidx.as<u32>(), M, nst, st);
+        }));
         RCHK(s->tb_head.reserve(M + 16, false));
         RCHK(s->tb_seg.reserve(M * 8, false));
         launch_pg_heads32(st, s->tb_skey.as<u32>(), M, s->tb_head.as<unsigned char>());
-        launch_slx_compact(st, 1, s->tb_head.as<unsigned char>(), nullptr, nullptr, nullptr, M, s->x_blk.as<int64_t>(),
-                           nullptr, nullptr, s->tb_seg.as<int64_t>());
-        HIPCHK(hipGetLastError());
         int64_t n_seg = 0;
-        RCHK(read_count(q, s->x_blk.as<int64_t>() + (M + kTile - 1) / kTile, &n_seg));
+        RCHK(compact_flags(q, s->tb_head.as<unsigned char>(), M, s->tb_seg.as<int64_t>(), &n_seg));
         // ---- a row per (chunk, group): the states fold their records from the carried values
         const int64_t rc = M;
         RCHK(s->xr_ts.reserve(rc * 8, false));
@@ -998,13 +860,10 @@ static int plane_run_tbsc(sh_query* q, const sh_batch* b, int64_t now, bool host
         n_rows &= 0xFFFFFFFFll;
         // ---- rows in (chunk, first record) order -> the output columns
         const unsigned rbits = (unsigned)(32 + bits_for(nch + 1));
-        tb = 0;
-        if (sort_u64_iota_bits(nullptr, &tb, s->tb_rkey.as<u64>(), nullptr, nullptr, n_rows, rbits, st))
-            return sh_fail(SH_ERR_DEVICE, "radix sort sizing failed");
-        RCHK(s->sort_tmp.reserve(std::max<size_t>(tb, 16), false));
-        if (sort_u64_iota_bits(s->sort_tmp.p, &tb, s->tb_rkey.as<u64>(), s->tb_rkey2.as<u64>(), s->tb_order.as<u32>(),
-                               n_rows, rbits, st))
-            return sh_fail(SH_ERR_DEVICE, "radix sort failed");
+        RCHK(with_sort_tmp(q, "radix sort", [&](void* tmp, size_t* tb) {
+            return sort_u64_iota_bits(tmp, tb, s->tb_rkey.as<u64>(), s->tb_rkey2.as<u64>(), s->tb_order.as<u32>(), n_rows,
+                                      rbits, st);
+        }));
         const int64_t oc = std::max<int64_t>(n_rows, 1);
         RCHK(s->out_ts.reserve(oc * 8, false));
         RCHK(s->out_keys.reserve((size_t)std::max(1, q->gkp.n) * oc * 8, false));
@@ -1027,16 +886,7 @@ static int plane_run_tbsc(sh_query* q, const sh_batch* b, int64_t now, bool host
         RCHK(sliding_flushes(q, n_rows, &n_flushes));
         s->tb_chunk_base += nch;
     }
-    q->seq += N;
-    q->clock = q->clock_valid ? std::max(q->clock, info.max_tl) : info.max_tl;
-    q->clock_valid = true;
-    q->stats.events = N;
-    HIPCHK(hipEventRecord(q->ev_push1, st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, q->ev_push0, q->ev_push1);
-    q->stats.push_ms = ms;
-    q->stats.main_kernel_bytes = M * (int64_t)(16 + 8 * V) + n_rows * (int64_t)(8 + 8 * na);
+    RCHK(push_done(q, b, info, M * (int64_t)(16 + 8 * V) + n_rows * (int64_t)(8 + 8 * na)));
     return sliding_output(q, n_rows, n_flushes, false, host_out, out);
 }
 
@@ -1163,21 +1013,14 @@ static int group_time_rows(sh_query* q, const ColSet* cs, SlRecords rec, int64_t
         // operations by state slot, each state's in its partition's order
         RCHK(s->pg_skey.reserve(oc * 4, false));
         RCHK(s->pg_sidx.reserve(oc * 4, false));
-        size_t tb = 0;
-        if (sort_slot_ranks(nullptr, &tb, O.pg, nullptr, nullptr, ocap, (int64_t)1 << 32, st))
-            return sh_fail(SH_ERR_DEVICE, "radix sort sizing failed");
-        RCHK(s->sort_tmp.reserve(std::max<size_t>(tb, 16), false));
-        if (sort_slot_ranks(s->sort_tmp.p, &tb, O.pg, s->pg_skey.as<u32>(), s->pg_sidx.as<u32>(), ocap, (int64_t)1 << 32, st))
-            return sh_fail(SH_ERR_DEVICE, "radix sort failed");
+        RCHK(with_sort_tmp(q, "radix sort", [&](void* tmp, size_t* tb) {
+            return sort_slot_ranks(tmp, tb, O.pg, s->pg_skey.as<u32>(), s->pg_sidx.as<u32>(), ocap, (int64_t)1 << 32, st);
+        }));
         RCHK(s->pg_head.reserve(n_ops + 16, false));
         RCHK(s->pg_seg.reserve(n_ops * 8, false));
-        RCHK(s->x_blk.reserve((size_t)((n_ops + kTile - 1) / kTile + 2) * 8, false));
         launch_pg_heads32(st, s->pg_skey.as<u32>(), n_ops, s->pg_head.as<unsigned char>());
-        launch_slx_compact(st, 1, s->pg_head.as<unsigned char>(), nullptr, nullptr, nullptr, n_ops, s->x_blk.as<int64_t>(),
-                           nullptr, nullptr, s->pg_seg.as<int64_t>());
-        HIPCHK(hipGetLastError());
         int64_t n_seg = 0;
-        RCHK(read_count(q, s->x_blk.as<int64_t>() + (n_ops + kTile - 1) / kTile, &n_seg));
+        RCHK(compact_flags(q, s->pg_head.as<unsigned char>(), n_ops, s->pg_seg.as<int64_t>(), &n_seg));
         // replay: at most one row per operation
         const int64_t rc = n_ops;
         RCHK(s->xr_ts.reserve(rc * 8, false));
@@ -1243,13 +1086,10 @@ static int group_time_rows(sh_query* q, const ColSet* cs, SlRecords rec, int64_t
             // rows in (chunk, first operation) order
             int pbits = 1;
             while (pbits < 31 && ((int64_t)1 << pbits) <= M + nF) pbits++;
-            size_t tb2 = 0;
-            if (sort_u64_iota_bits(nullptr, &tb2, s->pg_rkey.as<u64>(), nullptr, nullptr, n_rows, 32 + pbits, st))
-                return sh_fail(SH_ERR_DEVICE, "radix sort sizing failed");
-            RCHK(s->sort_tmp.reserve(std::max<size_t>(tb2, 16), false));
-            if (sort_u64_iota_bits(s->sort_tmp.p, &tb2, s->pg_rkey.as<u64>(), s->pg_rkey2.as<u64>(), s->pg_order.as<u32>(),
-                                   n_rows, 32 + pbits, st))
-                return sh_fail(SH_ERR_DEVICE, "radix sort failed");
+            RCHK(with_sort_tmp(q, "radix sort", [&](void* tmp, size_t* tb) {
+                return sort_u64_iota_bits(tmp, tb, s->pg_rkey.as<u64>(), s->pg_rkey2.as<u64>(), s->pg_order.as<u32>(), n_rows,
+                                          32 + pbits, st);
+            }));
         }
         const int64_t rcap = std::max<int64_t>(n_rows, 1);
         RCHK(s->out_ts.reserve(rcap * 8, false));
@@ -1300,84 +1140,30 @@ static int plane_run(sh_query* q, const sh_batch* b, int64_t now, bool host_out,
     }
     if (N >= (int64_t)0x7FFFFFF0ll) return sh_fail(SH_ERR_INVALID, "push larger than 2G events");
     HIPCHK(hipEventRecord(q->ev_push0, st));
-    const int64_t cap = std::max<int64_t>(N, 1);
-    RCHK(s->rec_raw.reserve(cap * 4, false));
-    RCHK(s->rec_slot.reserve(cap * 4, false));
-    RCHK(s->rec_clock.reserve(cap * 8, false));
-    RCHK(s->rec_pm.reserve(cap * 8, false));
-    RCHK(s->rec_ts.reserve(cap * 8, false));
-    RCHK(s->rec_vals.reserve((size_t)V * cap * 8, false));
-    RCHK(s->slot_cnt.reserve(s->nslots * 4, false));
-    HIPCHK(hipMemsetAsync(s->slot_cnt.p, 0, s->nslots * 4, st));
-    SlRecords rec{s->rec_raw.as<u32>(), s->rec_slot.as<u32>(), s->rec_clock.as<int64_t>(), s->rec_pm.as<int64_t>(),
-                  s->rec_ts.as<int64_t>(), s->rec_vals.as<u64>(), cap};
-    ColSet cs{};
-    cs.n = q->d.n_cols;
-    WinParams wp{};
-    int nblk = 0;
+    // (lanes keyed by the partition, every event passing: the records are sorted and the partition offsets and
+    // the ring need made from the sorted slots before the push's sync, instead of per-slot counts)
+    RecOpts ro;
+    ro.V = V;
+    ro.base = s->pm;
+    ro.presort = !q->group_other;
+    RecStage stg;
+    RCHK(records_launch(q, b, ro, &stg));
+    const SlRecords rec = stg.rec;
+    const ColSet& cs = stg.cs;
+    const int64_t cap = stg.cap;
     int64_t M = 0;
     SlInfo info{};
-    bool sorted_off = false;  // records sorted and partition offsets made before the push's sync
     if (b) {
-        for (int c = 0; c < q->d.n_cols; c++) { cs.type[c] = q->d.col_types[c]; cs.ptr[c] = b->cols[c]; }
-        nblk = (int)((N + kTile - 1) / kTile);
-        RCHK(s->blk_pass.reserve(nblk * 8, false));
-        RCHK(s->blk_tl.reserve(nblk * 8, false));
-        RCHK(s->blk_pm.reserve(nblk * 8, false));
-        wp.kind = SH_WIN_TIME;  // the clock / pass-count prefix of the sliding path
-        wp.clock_valid = q->clock_valid;
-        wp.clock0 = q->clock;
-        wp.send_size = ss;
-        wp.N = N;
-        wp.rec_seq = q->tune.sl_records_seq;
-        launch_sl_prefix(st, b->ts, cs, q->fp, wp, s->blk_pass.as<int64_t>(), s->blk_tl.as<int64_t>(),
-                         s->blk_pm.as<int64_t>(), nblk, s->info.as<SlInfo>());
-        // (lanes keyed by the partition, every event passing: the partition offsets and the ring need come
-        // from the sorted slots instead of per-slot counts)
-        sorted_off = !q->group_other && sl_records_seq_applies(q->fp, wp, q->ap);
-        launch_sl_records(st, b->ts, cs, q->fp, wp, q->kp, q->kt.dev(), q->ap, s->blk_pass.as<int64_t>(),
-                          s->blk_tl.as<int64_t>(), s->blk_pm.as<int64_t>(), s->pm, rec,
-                          sorted_off ? nullptr : s->slot_cnt.as<u32>(), nblk);
         if (sched) launch_pl_slot_key(st, cs, q->kp, q->kt.dev(), N, s->pl_key.as<int64_t>());
-        HIPCHK(hipMemsetAsync((char*)s->info.p + offsetof(SlInfo, need), 0, 8, st));
-        int64_t* need_dev = (int64_t*)((char*)s->info.p + offsetof(SlInfo, need));
-        if (sorted_off) {
-            RCHK(s->ranks.reserve(cap * 4, false));
-            RCHK(s->p_slot.reserve(cap * 4, false));
-            RCHK(s->key_off.reserve((size_t)(s->nslots + 1) * 4, false));
-            size_t tb = 0;
-            if (sort_slot_ranks(nullptr, &tb, rec.slot, nullptr, nullptr, N, s->nslots, st))
-                return sh_fail(SH_ERR_DEVICE, "radix sort sizing failed");
-            RCHK(s->sort_tmp.reserve(std::max<size_t>(tb, 16), false));
-            if (sort_slot_ranks(s->sort_tmp.p, &tb, rec.slot, s->p_slot.as<u32>(), s->ranks.as<u32>(), N, s->nslots, st))
-                return sh_fail(SH_ERR_DEVICE, "radix sort failed");
-            launch_counts_sorted(st, s->p_slot.as<u32>(), N, s->slot_cnt.as<u32>());
-        }
-        launch_sl_need(st, s->slot_cnt.as<u32>(), s->rlen.as<int64_t>(), s->nslots, need_dev);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(s->h_info, s->info.p, sizeof(SlInfo), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        RCHK(q->kt.check(st));
-        info = *s->h_info;
+        RCHK(records_wait(q, stg, &info));
         M = info.total_pass;
-        if (tm && info.need > s->rc) {
-            int64_t nrc = s->rc;
-            while (nrc < info.need) nrc <<= 1;
-            RCHK(size_rings(q, nrc));
-        }
+        if (tm && info.need > s->rc) RCHK(grow_rings(q, info.need));
     }
     // each partition's records in stream order
-    if (!sorted_off) {
+    if (!stg.presorted) {
         RCHK(s->ranks.reserve(cap * 4, false));
         RCHK(s->p_slot.reserve(cap * 4, false));
-        if (M > 0) {
-            size_t tb = 0;
-            if (sort_slot_ranks(nullptr, &tb, rec.slot, nullptr, nullptr, M, s->nslots, st))
-                return sh_fail(SH_ERR_DEVICE, "radix sort sizing failed");
-            RCHK(s->sort_tmp.reserve(std::max<size_t>(tb, 16), false));
-            if (sort_slot_ranks(s->sort_tmp.p, &tb, rec.slot, s->p_slot.as<u32>(), s->ranks.as<u32>(), M, s->nslots, st))
-                return sh_fail(SH_ERR_DEVICE, "radix sort failed");
-        }
+        if (M > 0) RCHK(sort_keyed(q, rec.slot, M));
     }
     RCHK(s->key_off.reserve((size_t)(s->nslots + 1) * 4, false));
     RCHK(s->tmp.reserve((size_t)((s->nslots + 1 + kTile - 1) / kTile + 16) * 8, false));
@@ -1389,36 +1175,14 @@ static int plane_run(sh_query* q, const sh_batch* b, int64_t now, bool host_out,
     if (sched) {
         std::vector<int64_t> calls_s, calls_c, calls_k, reg_r;
         if (b) {
-            const int64_t NS = ss > 0 ? (N + ss - 1) / ss : 1;
-            const int nbS = (int)((NS + kTile - 1) / kTile);
-            RCHK(s->x_sK.reserve(NS * 8, false));
-            RCHK(s->x_scb.reserve(NS * 8, false));
-            RCHK(s->x_slast.reserve(NS * 8, false));
-            RCHK(s->x_cK.reserve(NS * 8, false));
-            RCHK(s->x_cC.reserve(NS * 8, false));
-            RCHK(s->x_cS.reserve(NS * 8, false));
-            RCHK(s->x_blk.reserve((size_t)((std::max(NS, M) + kTile - 1) / kTile + 2) * 8, false));
-            launch_slx_sends(st, b->ts, cs, q->fp, wp, s->blk_pass.as<int64_t>(), s->blk_tl.as<int64_t>(), nblk,
-                             s->x_sK.as<int64_t>(), s->x_scb.as<int64_t>(), s->x_slast.as<int64_t>());
-            launch_slx_compact(st, 0, nullptr, s->x_sK.as<int64_t>(), s->x_scb.as<int64_t>(), s->x_slast.as<int64_t>(),
-                               NS, s->x_blk.as<int64_t>(), s->x_cK.as<int64_t>(), s->x_cC.as<int64_t>(),
-                               s->x_cS.as<int64_t>());
-            HIPCHK(hipGetLastError());
-            int64_t nC = 0;
-            RCHK(read_count(q, s->x_blk.as<int64_t>() + nbS, &nC));
-            RCHK(d2h(q, calls_s, s->x_cS.p, nC));
-            RCHK(d2h(q, calls_c, s->x_cC.p, nC));
-            RCHK(d2h(q, calls_k, s->x_cK.p, nC));
+            int64_t nC = 0, n_reg = 0;
+            RCHK(push_calls(q, b, stg, &nC, &calls_s, &calls_c, &calls_k));
             // notify registrations: the records that raise their partition's lastTimestamp
             RCHK(s->pl_reg.reserve(cap + 16, false));
             launch_pl_notify(st, s->key_off.as<u32>(), s->ranks.as<u32>(), s->nslots, rec.ts, s->pl_last_ts.as<int64_t>(),
                              s->pl_reg.as<unsigned char>());
             RCHK(s->x_idx.reserve(cap * 8, false));
-            launch_slx_compact(st, 1, s->pl_reg.as<unsigned char>(), nullptr, nullptr, nullptr, M,
-                               s->x_blk.as<int64_t>(), nullptr, nullptr, s->x_idx.as<int64_t>());
-            HIPCHK(hipGetLastError());
-            int64_t n_reg = 0;
-            RCHK(read_count(q, s->x_blk.as<int64_t>() + (M + kTile - 1) / kTile, &n_reg));
+            RCHK(compact_flags(q, s->pl_reg.as<unsigned char>(), M, s->x_idx.as<int64_t>(), &n_reg));
             RCHK(d2h(q, reg_r, s->x_idx.p, n_reg));
         } else {
             calls_s.push_back(0);
@@ -1516,20 +1280,10 @@ static int plane_run(sh_query* q, const sh_batch* b, int64_t now, bool host_out,
         HIPCHK(hipEventRecord(q->ev_agg1, st));
         int64_t n_flushes = 0;
         RCHK(sliding_flushes(q, n_rows, &n_flushes));
-        if (b) {
-            q->seq += N;
-            q->clock = q->clock_valid ? std::max(q->clock, info.max_tl) : info.max_tl;
-            q->clock_valid = true;
-            q->stats.events = N;
-        }
-        HIPCHK(hipEventRecord(q->ev_push1, st));
-        HIPCHK(hipStreamSynchronize(st));
-        float ms = 0, kms = 0;
-        (void)hipEventElapsedTime(&ms, q->ev_push0, q->ev_push1);
+        RCHK(push_done(q, b, info, M * (int64_t)(16 + 8 * V) + n_rows * (int64_t)(8 + 8 * na)));
+        float kms = 0;
         (void)hipEventElapsedTime(&kms, q->ev_agg0, q->ev_agg1);
-        q->stats.push_ms = ms;
         q->stats.main_kernel_ms = kms;
-        q->stats.main_kernel_bytes = M * (int64_t)(16 + 8 * V) + n_rows * (int64_t)(8 + 8 * na);
         return sliding_output(q, n_rows, n_flushes, false, host_out, out);
     }
     HIPCHK(hipEventRecord(q->ev_agg1, st));
@@ -1567,18 +1321,7 @@ static int plane_run(sh_query* q, const sh_batch* b, int64_t now, bool host_out,
     }
     int64_t n_flushes = 0;
     RCHK(sliding_flushes(q, n_rows, &n_flushes));
-    if (b) {
-        q->seq += N;
-        q->clock = q->clock_valid ? std::max(q->clock, info.max_tl) : info.max_tl;
-        q->clock_valid = true;
-        q->stats.events = N;
-    }
-    HIPCHK(hipEventRecord(q->ev_push1, st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, q->ev_push0, q->ev_push1);
-    q->stats.push_ms = ms;
-    q->stats.main_kernel_bytes = M * (int64_t)(16 + 8 * V) + n_rows * (int64_t)(8 + 8 * na);
+    RCHK(push_done(q, b, info, M * (int64_t)(16 + 8 * V) + n_rows * (int64_t)(8 + 8 * na)));
     return sliding_output(q, n_rows, n_flushes, false, host_out, out);
 }
 

@@ -148,7 +148,7 @@ void sliding_destroy(sh_query* q) {
                       &s->p_slot, &s->p_clock, &s->p_pm, &s->p_ts, &s->p_vals, &s->rows_ts,
                       &s->rows_slot, &s->rows_send, &s->rows_clock, &s->rows_vals, &s->rows_nulls, &s->blk_cnt,
                       &s->out_ts, &s->out_keys, &s->out_vals, &s->out_nulls, &s->out_send, &s->out_clock,
-                      &s->out_expired, &s->flush_off, &s->flush_clock, &s->iota, &s->rec_sclk, &s->sort_tmp, &s->key_off, &s->g_rank, &s->inv, &s->rows_k,
+                      &s->out_expired, &s->flush_off, &s->flush_clock, &s->iota, &s->rec_sclk, &s->sort_tmp, &s->key_off, &s->rows_k,
                       &s->rg, &s->upm, &s->useq, &s->upm2, &s->useq2, &s->npend, &s->npend2, &s->x_sK, &s->x_scb,
                       &s->x_slast, &s->x_cK, &s->x_cC, &s->x_cS, &s->x_fire, &s->x_keep, &s->x_idx, &s->x_fK,
                       &s->x_fC, &s->x_fS, &s->x_blk, &s->x_xop, &s->x_xch, &s->x_xts, &s->x_xclk, &s->x_aop,
@@ -175,19 +175,154 @@ static int sliding_finish(sh_query* q, int64_t M, int64_t rec_cap, int64_t need,
                           int64_t send_base, int64_t raw_base, bool want_order, bool host_out, const sh_out** out,
                           bool presorted = false);
 
-// the push's records sorted stably by key slot (p_slot, ranks) and room for the key offsets
-static int sort_keyed(sh_query* q, const u32* slot, int64_t M) {
+int sort_keyed(sh_query* q, const u32* slot, int64_t M) {
     SlidingImpl* s = q->sl;
-    hipStream_t st = q->ctx->stream;
-    size_t tb = 0;
-    if (sort_slot_ranks(nullptr, &tb, slot, nullptr, nullptr, M, s->nslots, st))
-        return sh_fail(SH_ERR_DEVICE, "radix sort sizing failed");
-    RCHK(s->sort_tmp.reserve(std::max<size_t>(tb, 16), false));
     RCHK(s->p_slot.reserve(M * 4, false));
     RCHK(s->ranks.reserve(M * 4, false));
     RCHK(s->key_off.reserve((size_t)(s->nslots + 1) * 4, false));
-    if (sort_slot_ranks(s->sort_tmp.p, &tb, slot, s->p_slot.as<u32>(), s->ranks.as<u32>(), M, s->nslots, st))
-        return sh_fail(SH_ERR_DEVICE, "radix sort failed");
+    return with_sort_tmp(q, "radix sort", [&](void* tmp, size_t* tb) {
+        return sort_slot_ranks(tmp, tb, slot, s->p_slot.as<u32>(), s->ranks.as<u32>(), M, s->nslots, q->ctx->stream);
+    });
+}
+
+int grow_rings(sh_query* q, int64_t need) {
+    int64_t nrc = q->sl->rc;
+    while (nrc < need) nrc <<= 1;
+    return size_rings(q, nrc);
+}
+
+int records_launch(sh_query* q, const sh_batch* b, const RecOpts& o, RecStage* R) {
+    SlidingImpl* s = q->sl;
+    hipStream_t st = q->ctx->stream;
+    const int64_t N = b ? b->n : 0, cap = std::max<int64_t>(N, 1);
+    // records of all passing events (capacity N; the exact count is known after the prefix scan)
+    RCHK(s->rec_raw.reserve(cap * 4, false));
+    RCHK(s->rec_slot.reserve(cap * 4, false));
+    RCHK(s->rec_clock.reserve(cap * 8, false));
+    RCHK(s->rec_pm.reserve(cap * 8, false));
+    RCHK(s->rec_ts.reserve(cap * 8, false));
+    RCHK(s->rec_vals.reserve((size_t)o.V * cap * 8, false));
+    RCHK(s->slot_cnt.reserve(s->nslots * 4, false));
+    HIPCHK(hipMemsetAsync(s->slot_cnt.p, 0, s->nslots * 4, st));  // (the prefix kernel does not touch it)
+    R->o = o;
+    R->cap = cap;
+    R->rec = SlRecords{s->rec_raw.as<u32>(), s->rec_slot.as<u32>(), s->rec_clock.as<int64_t>(), s->rec_pm.as<int64_t>(),
+                       s->rec_ts.as<int64_t>(), s->rec_vals.as<u64>(), cap};
+    if (o.aos) {
+        RCHK(s->rec_aos.reserve((size_t)cap * kSlAosWords * 8, false));
+        R->rec.aos = s->rec_aos.as<u64>();
+    }
+    // externalTime / length: the records' clock is not the playback clock, which rows take from rec_sclk
+    if (o.sclk) RCHK(s->rec_sclk.reserve(cap * 8, false));
+    R->cs = ColSet{};
+    R->cs.n = q->d.n_cols;
+    for (int c = 0; c < q->d.n_cols; c++) { R->cs.type[c] = q->d.col_types[c]; R->cs.ptr[c] = b ? b->cols[c] : nullptr; }
+    R->nblk = (int)((N + kTile - 1) / kTile);
+    WinParams& wp = R->wp;
+    wp = WinParams{};
+    wp.kind = o.kind;
+    wp.ts_col = o.ts_col;
+    wp.clock_valid = q->clock_valid;
+    wp.clock0 = q->clock;
+    wp.send_size = b ? b->send_size : 0;
+    wp.N = N;
+    wp.rec_seq = q->tune.sl_records_seq;  // (lane-strided records where they apply)
+    R->presorted = b && o.presort && sl_records_seq_applies(q->fp, wp, q->ap);
+    if (!b) return SH_OK;
+    RCHK(s->blk_pass.reserve(R->nblk * 8, false));
+    RCHK(s->blk_tl.reserve(R->nblk * 8, false));
+    RCHK(s->blk_pm.reserve(R->nblk * 8, false));
+    launch_sl_prefix(st, b->ts, R->cs, q->fp, wp, s->blk_pass.as<int64_t>(), s->blk_tl.as<int64_t>(),
+                     s->blk_pm.as<int64_t>(), R->nblk, s->info.as<SlInfo>());
+    // presorted: no per-slot counts here; the key offsets and the ring need come from the sorted slots
+    launch_sl_records(st, b->ts, R->cs, q->fp, wp, q->kp, q->kt.dev(), q->ap, s->blk_pass.as<int64_t>(),
+                      s->blk_tl.as<int64_t>(), s->blk_pm.as<int64_t>(), o.base, R->rec,
+                      R->presorted ? nullptr : s->slot_cnt.as<u32>(), R->nblk,
+                      o.sclk ? s->rec_sclk.as<int64_t>() : nullptr);
+    return SH_OK;
+}
+
+int records_wait(sh_query* q, const RecStage& R, SlInfo* info) {
+    SlidingImpl* s = q->sl;
+    hipStream_t st = q->ctx->stream;
+    const RecOpts& o = R.o;
+    int64_t* need_dev = (int64_t*)((char*)s->info.p + offsetof(SlInfo, need));
+    if (o.need) HIPCHK(hipMemsetAsync(need_dev, 0, 8, st));
+    if (o.timed) q->srt_timed = R.presorted;
+    if (R.presorted && o.sort) {
+        if (o.timed) HIPCHK(hipEventRecord(q->ev_srt0, st));  // (the sort is part of the replay's time)
+        RCHK(sort_keyed(q, R.rec.slot, R.wp.N));
+        if (o.timed) HIPCHK(hipEventRecord(q->ev_srt1, st));
+        launch_counts_sorted(st, s->p_slot.as<u32>(), R.wp.N, s->slot_cnt.as<u32>());
+    }
+    if (o.need) launch_sl_need(st, s->slot_cnt.as<u32>(), s->rlen.as<int64_t>(), s->nslots, need_dev);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(s->h_info, s->info.p, sizeof(SlInfo), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    RCHK(q->kt.check(st));
+    *info = *s->h_info;
+    return SH_OK;
+}
+
+int push_calls(sh_query* q, const sh_batch* b, const RecStage& R, int64_t* nC, std::vector<int64_t>* calls_s,
+               std::vector<int64_t>* calls_c, std::vector<int64_t>* calls_k) {
+    SlidingImpl* s = q->sl;
+    hipStream_t st = q->ctx->stream;
+    const int64_t ss = b->send_size, NS = ss > 0 ? (b->n + ss - 1) / ss : 1, nbS = (NS + kTile - 1) / kTile;
+    RCHK(s->x_sK.reserve(NS * 8, false));
+    RCHK(s->x_scb.reserve(NS * 8, false));
+    RCHK(s->x_slast.reserve(NS * 8, false));
+    RCHK(s->x_cK.reserve(NS * 8, false));
+    RCHK(s->x_cC.reserve(NS * 8, false));
+    RCHK(s->x_cS.reserve(NS * 8, false));
+    RCHK(s->x_blk.reserve((size_t)(nbS + 2) * 8, false));
+    launch_slx_sends(st, b->ts, R.cs, q->fp, R.wp, s->blk_pass.as<int64_t>(), s->blk_tl.as<int64_t>(), R.nblk,
+                     s->x_sK.as<int64_t>(), s->x_scb.as<int64_t>(), s->x_slast.as<int64_t>());
+    launch_slx_compact(st, 0, nullptr, s->x_sK.as<int64_t>(), s->x_scb.as<int64_t>(), s->x_slast.as<int64_t>(), NS,
+                       s->x_blk.as<int64_t>(), s->x_cK.as<int64_t>(), s->x_cC.as<int64_t>(), s->x_cS.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    RCHK(read_count(q, s->x_blk.as<int64_t>() + nbS, nC));
+    if (calls_s) RCHK(d2h(q, *calls_s, s->x_cS.p, *nC));
+    if (calls_c) RCHK(d2h(q, *calls_c, s->x_cC.p, *nC));
+    if (calls_k) RCHK(d2h(q, *calls_k, s->x_cK.p, *nC));
+    return SH_OK;
+}
+
+// x_blk is reserved here for n alone, whatever used it before: read_count has synchronised the stream by the
+// time a later reserve may replace the buffer, and DevBuf::reserve drains the stream before it frees a block.
+int compact_flags(sh_query* q, const unsigned char* flags, int64_t n, int64_t* idx_out, int64_t* count) {
+    SlidingImpl* s = q->sl;
+    const int64_t nb = (n + kTile - 1) / kTile;
+    RCHK(s->x_blk.reserve((size_t)(nb + 2) * 8, false));
+    launch_slx_compact(q->ctx->stream, 1, flags, nullptr, nullptr, nullptr, n, s->x_blk.as<int64_t>(), nullptr, nullptr,
+                       idx_out);
+    HIPCHK(hipGetLastError());
+    return read_count(q, s->x_blk.as<int64_t>() + nb, count);
+}
+
+int push_done(sh_query* q, const sh_batch* b, const SlInfo& info, int64_t bytes) {
+    hipStream_t st = q->ctx->stream;
+    if (b) {
+        q->seq += b->n;
+        q->clock = q->clock_valid ? std::max(q->clock, info.max_tl) : info.max_tl;
+        q->clock_valid = true;
+        q->stats.events = b->n;
+    }
+    HIPCHK(hipEventRecord(q->ev_push1, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, q->ev_push0, q->ev_push1);
+    q->stats.push_ms = ms;
+    q->stats.main_kernel_bytes = bytes;
+    return SH_OK;
+}
+
+int d2h(sh_query* q, std::vector<int64_t>& v, const void* dev, int64_t n) {
+    v.resize((size_t)std::max<int64_t>(n, 0));
+    if (n > 0) {
+        HIPCHK(hipMemcpyAsync(v.data(), dev, (size_t)n * 8, hipMemcpyDeviceToHost, q->ctx->stream));
+        HIPCHK(hipStreamSynchronize(q->ctx->stream));
+    }
     return SH_OK;
 }
 static int slx_run(sh_query* q, const sh_batch* b, int64_t now, bool host_out, const sh_out** out);
@@ -241,6 +376,22 @@ static int sliding_rekey(sh_query* q) {
 // / min / max-of-one-double shape with a min or max (sliding_keyed_ok)
 static bool keyed_aos(const sh_query* q) { return q->d.window == SH_WIN_TIME && sliding_keyed_ok(q->ap); }
 
+// the record stage of sliding_push and slx_run: the query's own window; externalTime / length keep the sends'
+// playback clock beside the records' clock, and length carries the passing count where the others carry PM
+static RecOpts sliding_rec_opts(const sh_query* q, bool aos, bool presort) {
+    const bool len = q->d.window == SH_WIN_LENGTH;
+    RecOpts o;
+    o.kind = q->d.window;  // SH_WIN_TIME, SH_WIN_EXT_TIME or SH_WIN_LENGTH
+    o.ts_col = q->d.ts_col;
+    o.V = std::max(1, q->ap.n_vcols);
+    o.aos = aos;
+    o.sclk = q->d.window == SH_WIN_EXT_TIME || len;
+    o.base = len ? q->sl->npass : q->sl->pm;
+    o.presort = presort;
+    o.timed = true;
+    return o;
+}
+
 int sliding_push(sh_query* q, const sh_batch* b, bool host_out, const sh_out** out) {
     SlidingImpl* s = q->sl;
     if (s->lane) return plane_push(q, b, host_out, out);
@@ -261,66 +412,14 @@ int sliding_push(sh_query* q, const sh_batch* b, bool host_out, const sh_out** o
     }
     if (s->xm) return slx_run(q, b, 0, host_out, out);
     HIPCHK(hipEventRecord(q->ev_push0, st));
-    ColSet cs{};
-    cs.n = q->d.n_cols;
-    for (int c = 0; c < q->d.n_cols; c++) { cs.type[c] = q->d.col_types[c]; cs.ptr[c] = b->cols[c]; }
-    int nblk = (int)((N + kTile - 1) / kTile);
-    RCHK(s->blk_pass.reserve(nblk * 8, false));
-    RCHK(s->blk_tl.reserve(nblk * 8, false));
-    RCHK(s->blk_pm.reserve(nblk * 8, false));
-    WinParams wp{};
-    wp.kind = q->d.window;  // SH_WIN_TIME, SH_WIN_EXT_TIME or SH_WIN_LENGTH
-    wp.ts_col = q->d.ts_col;
-    wp.clock_valid = q->clock_valid;
-    wp.clock0 = q->clock;
-    wp.send_size = b->send_size;
-    wp.N = N;
-    wp.rec_seq = q->tune.sl_records_seq;
-    launch_sl_prefix(st, b->ts, cs, q->fp, wp, s->blk_pass.as<int64_t>(), s->blk_tl.as<int64_t>(),
-                     s->blk_pm.as<int64_t>(), nblk, s->info.as<SlInfo>());
-    // records of all passing events (capacity N; the exact count is known after the prefix scan)
-    int V = std::max(1, q->ap.n_vcols);
-    RCHK(s->rec_raw.reserve(N * 4, false));
-    RCHK(s->rec_slot.reserve(N * 4, false));
-    RCHK(s->rec_clock.reserve(N * 8, false));
-    RCHK(s->rec_pm.reserve(N * 8, false));
-    RCHK(s->rec_ts.reserve(N * 8, false));
-    RCHK(s->rec_vals.reserve((size_t)V * N * 8, false));
-    RCHK(s->slot_cnt.reserve(s->nslots * 4, false));
     // keyed replay over lane-strided records (every event passes, M = N): the records are sorted by key
     // slot right away and the key offsets and ring need come from the sorted slots (no per-slot counts)
-    const bool pre = keyed_aos(q) && sl_records_seq_applies(q->fp, wp, q->ap);
-    HIPCHK(hipMemsetAsync(s->slot_cnt.p, 0, s->nslots * 4, st));
-    SlRecords rec{s->rec_raw.as<u32>(), s->rec_slot.as<u32>(), s->rec_clock.as<int64_t>(), s->rec_pm.as<int64_t>(),
-                  s->rec_ts.as<int64_t>(), s->rec_vals.as<u64>(), N};
-    if (keyed_aos(q)) {
-        RCHK(s->rec_aos.reserve((size_t)N * kSlAosWords * 8, false));
-        rec.aos = s->rec_aos.as<u64>();
-    }
-    // externalTime / length: the records' clock is not the playback clock, which rows take from rec_sclk
-    const bool len = q->d.window == SH_WIN_LENGTH;
-    const bool ext = q->d.window == SH_WIN_EXT_TIME || len;
-    if (ext) RCHK(s->rec_sclk.reserve(N * 8, false));
-    launch_sl_records(st, b->ts, cs, q->fp, wp, q->kp, q->kt.dev(), q->ap, s->blk_pass.as<int64_t>(),
-                      s->blk_tl.as<int64_t>(), s->blk_pm.as<int64_t>(), len ? s->npass : s->pm, rec,
-                      pre ? nullptr : s->slot_cnt.as<u32>(), nblk, ext ? s->rec_sclk.as<int64_t>() : nullptr);
-    HIPCHK(hipMemsetAsync((char*)s->info.p + offsetof(SlInfo, need), 0, 8, st));
-    int64_t* need_dev = (int64_t*)((char*)s->info.p + offsetof(SlInfo, need));
-    q->srt_timed = pre;
-    if (pre) {
-        HIPCHK(hipEventRecord(q->ev_srt0, st));  // (the sort is part of the replay's time)
-        RCHK(sort_keyed(q, rec.slot, N));
-        HIPCHK(hipEventRecord(q->ev_srt1, st));
-        launch_counts_sorted(st, s->p_slot.as<u32>(), N, s->slot_cnt.as<u32>());
-    }
-    launch_sl_need(st, s->slot_cnt.as<u32>(), s->rlen.as<int64_t>(), s->nslots, need_dev);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s->h_info, s->info.p, sizeof(SlInfo), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    RCHK(q->kt.check(st));
-    SlInfo info = *s->h_info;
+    RecStage stg;
+    RCHK(records_launch(q, b, sliding_rec_opts(q, keyed_aos(q), keyed_aos(q)), &stg));
+    SlInfo info{};
+    RCHK(records_wait(q, stg, &info));
     RCHK(sliding_finish(q, info.total_pass, N, info.need, b->send_size, s->send_base, q->seq, false, host_out, out,
-                        pre));
+                        stg.presorted));
     q->seq += N;
     // window state moves on
     q->clock = q->clock_valid ? std::max(q->clock, info.max_tl) : info.max_tl;
@@ -389,11 +488,7 @@ static int sliding_finish(sh_query* q, int64_t M, int64_t rec_cap, int64_t need,
     SlRecords rec{s->rec_raw.as<u32>(), s->rec_slot.as<u32>(), s->rec_clock.as<int64_t>(), s->rec_pm.as<int64_t>(),
                   s->rec_ts.as<int64_t>(), s->rec_vals.as<u64>(), rec_cap};
     if (keyed_aos(q)) rec.aos = s->rec_aos.as<u64>();
-    if (need > s->rc) {
-        int64_t nrc = s->rc;
-        while (nrc < need) nrc <<= 1;
-        RCHK(size_rings(q, nrc));
-    }
+    if (need > s->rc) RCHK(grow_rings(q, need));
     int64_t n_rows = 0;
     if (M > 0) {
         const int na = q->ap.n;
@@ -504,11 +599,9 @@ static int sliding_finish(sh_query* q, int64_t M, int64_t rec_cap, int64_t need,
     // flush structure: a flush per send that produced rows (one selector output chunk per send)
     int64_t n_flushes = 0;
     RCHK(sliding_flushes(q, n_rows, &n_flushes, send_size == 1));
-    HIPCHK(hipEventRecord(q->ev_push1, st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, q->ev_push0, q->ev_push1);
-    q->stats.push_ms = ms;
+    // (the sequence and the clock move on with the caller: sliding_push)
+    RCHK(push_done(q, nullptr, SlInfo{},
+                   M * (int64_t)(4 + 8 + 8 + 8 + 8 * q->ap.n_vcols) + n_rows * (int64_t)(8 + 8 * q->ap.n)));
     if (M > 0) {
         float ams = 0;
         (void)hipEventElapsedTime(&ams, q->ev_agg0, q->ev_agg1);
@@ -519,7 +612,6 @@ static int sliding_finish(sh_query* q, int64_t M, int64_t rec_cap, int64_t need,
         }
         q->stats.main_kernel_ms = ams;
     }
-    q->stats.main_kernel_bytes = M * (int64_t)(4 + 8 + 8 + 8 + 8 * q->ap.n_vcols) + n_rows * (int64_t)(8 + 8 * q->ap.n);
     return sliding_output(q, n_rows, n_flushes, want_order, host_out, out);
 }
 
@@ -690,88 +782,25 @@ static int slx_run(sh_query* q, const sh_batch* b, int64_t now, bool host_out, c
     }
     if (N >= (int64_t)0x7FFFFFF0ll) return sh_fail(SH_ERR_INVALID, "push larger than 2G events");
     HIPCHK(hipEventRecord(q->ev_push0, st));
-    ColSet cs{};
-    cs.n = q->d.n_cols;
-    WinParams wp{};
-    int nblk = 0;
+    // (lane-strided records, every event passes: sorted by key slot right away, offsets and ring need from
+    // the sorted slots instead of per-slot counts)
+    RecStage stg;
+    RCHK(records_launch(q, b, sliding_rec_opts(q, false, q->ap.n > 0), &stg));
+    const SlRecords rec = stg.rec;
+    const int64_t cap = stg.cap;
+    const bool presorted = stg.presorted;
     int64_t M = 0;
     SlInfo info{};
-    bool presorted = false;
-    const int64_t cap = std::max<int64_t>(N, 1);
-    RCHK(s->rec_raw.reserve(cap * 4, false));
-    RCHK(s->rec_slot.reserve(cap * 4, false));
-    RCHK(s->rec_clock.reserve(cap * 8, false));
-    RCHK(s->rec_pm.reserve(cap * 8, false));
-    RCHK(s->rec_ts.reserve(cap * 8, false));
-    RCHK(s->rec_vals.reserve((size_t)V * cap * 8, false));
-    RCHK(s->slot_cnt.reserve(s->nslots * 4, false));
-    HIPCHK(hipMemsetAsync(s->slot_cnt.p, 0, s->nslots * 4, st));
-    SlRecords rec{s->rec_raw.as<u32>(), s->rec_slot.as<u32>(), s->rec_clock.as<int64_t>(), s->rec_pm.as<int64_t>(),
-                  s->rec_ts.as<int64_t>(), s->rec_vals.as<u64>(), cap};
     if (b) {
-        for (int c = 0; c < q->d.n_cols; c++) { cs.type[c] = q->d.col_types[c]; cs.ptr[c] = b->cols[c]; }
-        nblk = (int)((N + kTile - 1) / kTile);
-        RCHK(s->blk_pass.reserve(nblk * 8, false));
-        RCHK(s->blk_tl.reserve(nblk * 8, false));
-        RCHK(s->blk_pm.reserve(nblk * 8, false));
-        wp.kind = q->d.window;
-        wp.ts_col = q->d.ts_col;
-        wp.clock_valid = q->clock_valid;
-        wp.clock0 = q->clock;
-        wp.send_size = ss;
-        wp.N = N;
-        wp.rec_seq = q->tune.sl_records_seq;  // (lane-strided records where they apply)
-        launch_sl_prefix(st, b->ts, cs, q->fp, wp, s->blk_pass.as<int64_t>(), s->blk_tl.as<int64_t>(),
-                         s->blk_pm.as<int64_t>(), nblk, s->info.as<SlInfo>());
-        if (ext) RCHK(s->rec_sclk.reserve(cap * 8, false));
-        // (lane-strided records, every event passes: sorted by key slot right away, offsets and ring need
-        // from the sorted slots instead of per-slot counts)
-        presorted = q->ap.n > 0 && sl_records_seq_applies(q->fp, wp, q->ap);
-        launch_sl_records(st, b->ts, cs, q->fp, wp, q->kp, q->kt.dev(), q->ap, s->blk_pass.as<int64_t>(),
-                          s->blk_tl.as<int64_t>(), s->blk_pm.as<int64_t>(), len ? s->npass : s->pm, rec,
-                          presorted ? nullptr : s->slot_cnt.as<u32>(), nblk, ext ? s->rec_sclk.as<int64_t>() : nullptr);
-        HIPCHK(hipMemsetAsync((char*)s->info.p + offsetof(SlInfo, need), 0, 8, st));
-        int64_t* need_dev = (int64_t*)((char*)s->info.p + offsetof(SlInfo, need));
-        q->srt_timed = presorted;
-        if (presorted) {
-            HIPCHK(hipEventRecord(q->ev_srt0, st));
-            RCHK(sort_keyed(q, rec.slot, N));
-            HIPCHK(hipEventRecord(q->ev_srt1, st));
-            launch_counts_sorted(st, s->p_slot.as<u32>(), N, s->slot_cnt.as<u32>());
-        }
-        launch_sl_need(st, s->slot_cnt.as<u32>(), s->rlen.as<int64_t>(), s->nslots, need_dev);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(s->h_info, s->info.p, sizeof(SlInfo), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        RCHK(q->kt.check(st));
-        info = *s->h_info;
+        RCHK(records_wait(q, stg, &info));
         M = info.total_pass;
-        if (info.need > s->rc) {
-            int64_t nrc = s->rc;
-            while (nrc < info.need) nrc <<= 1;
-            RCHK(size_rings(q, nrc));
-        }
+        if (info.need > s->rc) RCHK(grow_rings(q, info.need));
     }
     // ---- the calls of the push (sends that set the clock) and which of them fire a TIMER chunk
     int64_t nC = 0, nF = 0, n_keep = 0;
     if (!ext) {
         if (b) {
-            const int64_t NS = ss > 0 ? (N + ss - 1) / ss : 1;
-            const int nbS = (int)((NS + kTile - 1) / kTile);
-            RCHK(s->x_sK.reserve(NS * 8, false));
-            RCHK(s->x_scb.reserve(NS * 8, false));
-            RCHK(s->x_slast.reserve(NS * 8, false));
-            RCHK(s->x_cK.reserve(NS * 8, false));
-            RCHK(s->x_cC.reserve(NS * 8, false));
-            RCHK(s->x_cS.reserve(NS * 8, false));
-            RCHK(s->x_blk.reserve((size_t)(nbS + 2) * 8, false));
-            launch_slx_sends(st, b->ts, cs, q->fp, wp, s->blk_pass.as<int64_t>(), s->blk_tl.as<int64_t>(), nblk,
-                             s->x_sK.as<int64_t>(), s->x_scb.as<int64_t>(), s->x_slast.as<int64_t>());
-            launch_slx_compact(st, 0, nullptr, s->x_sK.as<int64_t>(), s->x_scb.as<int64_t>(), s->x_slast.as<int64_t>(),
-                               NS, s->x_blk.as<int64_t>(), s->x_cK.as<int64_t>(), s->x_cC.as<int64_t>(),
-                               s->x_cS.as<int64_t>());
-            HIPCHK(hipGetLastError());
-            RCHK(read_count(q, s->x_blk.as<int64_t>() + nbS, &nC));
+            RCHK(push_calls(q, b, stg, &nC, nullptr, nullptr, nullptr));
         } else {
             nC = 1;
             RCHK(s->x_cK.reserve(8, false));
@@ -793,21 +822,14 @@ static int slx_run(sh_query* q, const sh_batch* b, int64_t now, bool host_out, c
         RCHK(s->x_fC.reserve(std::max<int64_t>(nC, 1) * 8, false));
         RCHK(s->x_fS.reserve(std::max<int64_t>(nC, 1) * 8, false));
         RCHK(s->npend2.reserve(std::max<int64_t>(n_cand, 1) * 8, false));
-        RCHK(s->x_blk.reserve((size_t)((n_big + kTile - 1) / kTile + 2) * 8, false));
         HIPCHK(hipMemsetAsync(s->x_fire.p, 0, nC + 16, st));
         launch_slx_notify(st, s->npend.as<int64_t>(), s->n_np, rec.pm, M, s->pm, s->x_cK.as<int64_t>(),
                           s->x_cC.as<int64_t>(), nC, T, s->x_fire.as<unsigned char>(), s->x_keep.as<unsigned char>());
-        launch_slx_compact(st, 1, s->x_fire.as<unsigned char>(), nullptr, nullptr, nullptr, nC, s->x_blk.as<int64_t>(),
-                           nullptr, nullptr, s->x_idx.as<int64_t>());
-        HIPCHK(hipGetLastError());
-        RCHK(read_count(q, s->x_blk.as<int64_t>() + (nC + kTile - 1) / kTile, &nF));
+        RCHK(compact_flags(q, s->x_fire.as<unsigned char>(), nC, s->x_idx.as<int64_t>(), &nF));
         launch_slx_gather_calls(st, s->x_idx.as<int64_t>(), nF, s->x_cK.as<int64_t>(), s->x_cC.as<int64_t>(),
                                 s->x_cS.as<int64_t>(), s->x_fK.as<int64_t>(), s->x_fC.as<int64_t>(),
                                 s->x_fS.as<int64_t>());
-        launch_slx_compact(st, 1, s->x_keep.as<unsigned char>(), nullptr, nullptr, nullptr, n_cand,
-                           s->x_blk.as<int64_t>(), nullptr, nullptr, s->x_idx.as<int64_t>());
-        HIPCHK(hipGetLastError());
-        RCHK(read_count(q, s->x_blk.as<int64_t>() + (n_cand + kTile - 1) / kTile, &n_keep));
+        RCHK(compact_flags(q, s->x_keep.as<unsigned char>(), n_cand, s->x_idx.as<int64_t>(), &n_keep));
         launch_slx_gather_pend(st, s->x_idx.as<int64_t>(), n_keep, s->npend.as<int64_t>(), s->n_np, rec.pm,
                                s->npend2.as<int64_t>());
         if (!b && nF == 0) {
@@ -960,19 +982,10 @@ static int slx_run(sh_query* q, const sh_batch* b, int64_t now, bool host_out, c
     s->npass += M;
     s->w0 = new_w;
     if (b) {
-        q->seq += N;
-        q->clock = q->clock_valid ? std::max(q->clock, info.max_tl) : info.max_tl;
-        q->clock_valid = true;
         s->pm = std::max(s->pm, info.max_pm);
         s->send_base += ss > 0 ? (N + ss - 1) / ss : 1;
-        q->stats.events = N;
     }
-    HIPCHK(hipEventRecord(q->ev_push1, st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, q->ev_push0, q->ev_push1);
-    q->stats.push_ms = ms;
-    q->stats.main_kernel_bytes = n_ops * (int64_t)(16 + 8 * V) + n_rows * (int64_t)(8 + 8 * na);
+    RCHK(push_done(q, b, info, n_ops * (int64_t)(16 + 8 * V) + n_rows * (int64_t)(8 + 8 * na)));
     return sliding_output(q, n_rows, n_flushes, false, host_out, out);
 }
 

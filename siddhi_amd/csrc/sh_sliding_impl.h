@@ -1,9 +1,11 @@
 // sh_sliding_impl.h — host state of a query of kind 1 (sh_sliding.cpp: time / externalTime / length windows;
 // sh_plane.cpp: partitioned lengthBatch / time windows keyed by the partition).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <deque>
 #include <set>
+#include <string>
 #include <tuple>
 #include <unordered_map>
 #include <vector>
@@ -38,7 +40,7 @@ struct SlidingImpl {
     DevBuf blk_pass, blk_tl, blk_pm, info, rec_raw, rec_slot, rec_clock, rec_pm, rec_ts, rec_vals, slot_cnt, counts,
         tmp, ranks, part_off, flags, rec_sclk, p_raw, p_slot, p_clock, p_pm, p_ts, p_vals, rows_ts, rows_rep, rows_slot, rows_send, rows_clock, rows_vals, rows_nulls, blk_cnt, out_ts,
         out_keys, out_vals, out_nulls, out_send, out_clock, out_expired, out_rep, flush_off, flush_clock, sort_tmp,
-        key_off, g_rank, inv, rows_k, rec_aos;
+        key_off, rows_k, rec_aos;
     SlInfo* h_info = nullptr;
     PinnedBuf h_up;  // pinned staging of small host->device uploads
     sh_out dev_out{};
@@ -117,6 +119,62 @@ int empty_out(sh_query* q, const sh_out** out);
 int sliding_flushes(sh_query* q, int64_t n_rows, int64_t* n_flushes_out, bool per_row = false);
 int sliding_output(sh_query* q, int64_t n_rows, int64_t n_flushes, bool want_order, bool host_out, const sh_out** out);
 int read_count(sh_query* q, const int64_t* dev, int64_t* out);
+int d2h(sh_query* q, std::vector<int64_t>& v, const void* dev, int64_t n);  // host copy of n i64 (synchronises)
+
+// ---- the front end of a push, shared by sliding_push, slx_run and the lanes (sh_sliding.cpp) ----
+// What differs between the callers of the record stage:
+struct RecOpts {
+    int kind = SH_WIN_TIME, ts_col = 0;  // WinParams: the lanes take the time window's clock / pass-count prefix
+    int V = 1;             // value columns of a record
+    bool aos = false;      // rec_aos too (the keyed replay's 48-byte records)
+    bool sclk = false;     // rec_sclk too (externalTime / length: the sends' playback clock)
+    int64_t base = 0;      // carried into the records kernel: npass for length, pm otherwise
+    bool presort = false;  // the caller's own condition for records that are sorted by slot at once; it takes
+                           // effect where the lane-strided records apply (every event passes, M = N):
+                           // RecStage::presorted, and the records kernel then counts no slots
+    bool sort = true;      // presorted: records_wait sorts and counts (lane 3 sorts later, carried records included)
+    bool timed = false;    // ... between ev_srt0 / ev_srt1, with q->srt_timed (the sliding callers)
+    bool need = true;      // SlInfo.need, the ring capacity the push needs
+};
+struct RecStage {
+    shd::ColSet cs;
+    shd::WinParams wp;
+    int nblk;
+    shd::SlRecords rec;
+    int64_t cap;
+    bool presorted;
+    RecOpts o;
+};
+// Reserves the rec_* buffers and slot_cnt (zeroed) and builds the stage's views; with a batch also the prefix
+// scan and the records kernel. b == nullptr (a TIMER call): the empty views only.
+int records_launch(sh_query* q, const sh_batch* b, const RecOpts& o, RecStage* R);
+// The rest of the stage, behind whatever the caller enqueued after the records: the presorted sort and counts,
+// the ring need, then SlInfo on the host (the push's one sync here) and the key table's check.
+int records_wait(sh_query* q, const RecStage& R, SlInfo* info);
+int grow_rings(sh_query* q, int64_t need);  // size_rings to the power of two that holds `need`
+// the push's records sorted stably by key slot (p_slot, ranks) and room for the key offsets
+int sort_keyed(sh_query* q, const uint32_t* slot, int64_t M);
+// The push's calls — the sends that set the clock — on the device (x_cK, x_cC, x_cS), *nC of them; host copies
+// into the vectors that are not null.
+int push_calls(sh_query* q, const sh_batch* b, const RecStage& R, int64_t* nC, std::vector<int64_t>* calls_s,
+               std::vector<int64_t>* calls_c, std::vector<int64_t>* calls_k);
+// indices of the set flags among n -> idx_out (reserved by the caller), their number -> *count
+int compact_flags(sh_query* q, const unsigned char* flags, int64_t n, int64_t* idx_out, int64_t* count);
+// The push's epilogue: sequence and clock move on (with a batch), stats.events, ev_push1 and the final sync,
+// push_ms and main_kernel_bytes.
+int push_done(sh_query* q, const sh_batch* b, const SlInfo& info, int64_t bytes);
+
+// A two-call (size, then run) library operation in sort_tmp: run(temp, &bytes) is called with temp == nullptr
+// for the size and with the reserved buffer to do the work; non-zero is a failure.
+template <typename F>
+int with_sort_tmp(sh_query* q, const char* what, F run) {
+    size_t tb = 0;
+    if (run((void*)nullptr, &tb)) return sh_fail(SH_ERR_DEVICE, std::string(what) + " sizing failed");
+    if (int r = q->sl->sort_tmp.reserve(std::max<size_t>(tb, 16), false)) return r;
+    if (run(q->sl->sort_tmp.p, &tb)) return sh_fail(SH_ERR_DEVICE, std::string(what) + " failed");
+    return SH_OK;
+}
+
 int plane_create(sh_query* q);
 int plane_push(sh_query* q, const sh_batch* b, bool host_out, const sh_out** out);
 int plane_advance(sh_query* q, int64_t now, const sh_out** out, bool host_out);
